@@ -9,8 +9,11 @@ One "step" = one pass of the hot path over one synthetic batch (BASELINE.json co
 on N_per_gpu = 100,000 patients x T = 200 steps, fp64, inputs resident in HBM (generated on
 device before timing).  Weak scaling: every rank holds its own 100k-patient shard.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
        (N > 1: torchrun --nproc-per-node N bench.py --gpus N ...)
+
+A run sets up, warms up, times K steps and prints one JSON line (value, ms_per_step, ...).  --full adds what is
+measured beside that figure: CPU baselines, oracle parity, per-kernel rooflines, the north-star and C3 blocks.
 """
 from __future__ import annotations
 
@@ -117,7 +120,7 @@ def parse():
                     help="C2 fused: one cohort re-read every step (default: two cohorts alternate, so no step "
                          "re-reads data the 256 MB Infinity Cache still holds)")
     ap.add_argument("--isolated", action="store_true",
-                    help="also time each C2 kernel in isolation (back-to-back launches on one stream)")
+                    help="with --full: also time each C2 kernel in isolation (back-to-back launches on one stream)")
     ap.add_argument("--config", default="c2", choices=["c2", "c3", "c4", "c5", "insite", "insite4", "f4", "ns"],
                     help="c2: BASELINE configs[1], the headline line (default); c3: configs[2], the 5-state fp32 "
                          "system (parity-test configuration, measured separately)")
@@ -129,9 +132,22 @@ def parse():
                          "comparisons; for counter runs)")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic_r02.json"),
                     help="per-launch HBM bytes from the rocprofv3 PMC passes (profiles/), if present")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything beside the headline figure: the CPU baselines, the "
+                         "oracle parity of the benched cohort, the instrumented per-kernel / roofline passes, the "
+                         "alternative routes timed beside the product's, and (default C2 line) the north-star and C3 "
+                         "blocks.  Without it a run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the arrays the last timed step returned to DIR/<name>.npy "
+                         "(float32 / float64; an output over the size budget as a fixed seeded sample of its rows, "
+                         "the rows in <name>_index.npy); the inputs depend on the arguments alone, so two builds "
+                         "can be compared output for output")
     args = ap.parse_args()
     if args.warmup is None:
         args.warmup = WARMUP_DEFAULT.get(args.config, 5)
+    if not args.full:
+        args.no_cpu_baseline = args.no_parity = args.no_north_star = args.no_c3_block = args.no_fused = True
+        args.insite_only_binned = True
     return args
 
 
@@ -196,6 +212,37 @@ def gram_bytes(N, L, U=2, w=8):
     """Algorithmic HBM bytes of one discovery pass: the L = T observations of every patient
     (x[p, 0..L-1] feed the L-1 rows' smoothing stencils) + statics, arm byte and row count."""
     return N * L * w + N * (U * w + 1 + 4)
+
+
+def headline(args, value, ms_step, n_gpus, scaling, dtype, data, workload):
+    """The result line of a run without --full: the headline figure and what it was measured on."""
+    return {"metric": METRIC, "value": value, "unit": "patient-trajectories/s", "n_gpus": n_gpus, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True, "scaling": scaling,
+            "vs_baseline": None, "dtype": dtype, "data": data, "config": {"workload": workload}}
+
+
+DUMP_BUDGET = 48 << 20     # bytes the sampled outputs of --dump-outputs share (64 MB in all with the small arrays)
+
+
+def dump_outputs(args, arrays):
+    """--dump-outputs: write the last timed step's outputs (call right after the timed region, before any later pass
+    reuses the buffers).  ``arrays`` maps a name to a tensor, or to (tensor, axis) for an output that can exceed the
+    budget: that one is written as a fixed seeded sample of its slices along ``axis``, the sampled positions in
+    <name>_index.npy.  float32 stays float32, every other dtype is written as float64."""
+    if not args.dump_outputs:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    share = DUMP_BUDGET // max(1, sum(isinstance(v, tuple) for v in arrays.values()))
+    for name, v in arrays.items():
+        t, axis = v if isinstance(v, tuple) else (v, None)
+        w = 4 if t.dtype == torch.float32 else 8
+        if axis is not None and t.numel() * w > share:
+            n = t.size(axis)
+            idx = np.sort(np.random.default_rng(0).choice(n, max(1, share // (t.numel() // n * w)), replace=False))
+            t = t.index_select(axis, torch.as_tensor(idx, device=t.device))
+            np.save(os.path.join(args.dump_outputs, name + "_index.npy"), idx.astype(np.float64))
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a if a.dtype == np.float32 else a.astype(np.float64))
 
 
 # --------------------------------------------------------------------------------------------------
@@ -422,15 +469,16 @@ def c3_main(args):
         cpu = c3_cpu_baseline(max(64, min(2000, args.cpu_sample // 50)), T, args.seed + 3)
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    out = c3_measure(args, dev, N, T, args.steps, args.warmup, not args.no_parity)
+    out = c3_measure(args, dev, N, T, args.steps, args.warmup, not args.no_parity, dump=True)
     if cpu is not None:
         out["cpu_baseline"] = cpu
     emit(out)
 
 
-def c3_measure(args, dev, N, T, steps, warmup, parity=True):
+def c3_measure(args, dev, N, T, steps, warmup, parity=True, dump=False):
     """The C3 line's measurement (c3_main; also the compact ``c3`` block of the default C2 line):
-    ``steps`` timed discovery + rollout steps after ``warmup``, per-kernel HIP-event averages, the oracle parity."""
+    ``steps`` timed discovery + rollout steps after ``warmup`` and, with --full, per-kernel HIP-event averages and the
+    oracle parity."""
     from insite_amd import multistate as MS
     coh = MS.synthetic_c3(N, T, seed=args.seed, device=dev)
     g = torch.Generator(device=dev)
@@ -469,6 +517,14 @@ def c3_measure(args, dev, N, T, steps, warmup, parity=True):
         roll()
     torch.cuda.synchronize(dev)
     ms_step = (time.perf_counter() - t0) / steps * 1e3
+    if dump:
+        dump_outputs(args, {"G": G, "B": B, "coef": coef, "mask": mask, "iters": iters, "y": (y, 2)})
+    dtype = "f32 (storage, rollout) / f64 (Gram, STLSQ)"
+    data = "synthetic: on-device C3 cohort (planted 5-state system, Markov treatment, RK4-10 truth)"
+    workload = (f"C3: 5-state + binary treatment, {N // 1000}k patients x {T} steps: discovery "
+                f"(S-state Gram on f64 MFMA + STLSQ per state) + RK4 counterfactual rollout")
+    if not args.full:
+        return headline(args, N / (ms_step * 1e-3), ms_step, 1, "weak", dtype, data, workload)
 
     def timed(fn, n):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -502,11 +558,8 @@ def c3_measure(args, dev, N, T, steps, warmup, parity=True):
     out = {
         "metric": METRIC, "value": N / (ms_step * 1e-3), "unit": "patient-trajectories/s", "n_gpus": 1,
         "steps": steps, "warmup": warmup, "ms_per_step": ms_step, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f32 (storage, rollout) / f64 (Gram, STLSQ)",
-        "data": "synthetic: on-device C3 cohort (planted 5-state system, Markov treatment, RK4-10 truth)",
-        "config": {"workload": f"C3: 5-state + binary treatment, {N // 1000}k patients x {T} steps: discovery "
-                               f"(S-state Gram on f64 MFMA + STLSQ per state) + RK4 counterfactual rollout",
-                   "patients": N, "T": T, "states": S, "library_terms": F,
+        "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": data,
+        "config": {"workload": workload, "patients": N, "T": T, "states": S, "library_terms": F,
                    "support_equals_truth": bool(torch.equal(mask != 0, truth != 0))},
         "roofline": {"kernel": "gram_ms4_kernel", "bound": "mfma", "achieved": gflop / (gram_ms_t * 1e-3) / 1e12,
                      "peak": 78.6, "unit": "TFLOP/s", "frac": gflop / (gram_ms_t * 1e-3) / 1e12 / 78.6,
@@ -667,6 +720,17 @@ def c5_main(args):
     if world > 1:
         dist.barrier()
     ms_step = idist.max_over_ranks(time.perf_counter() - t0, dev) / args.steps * 1e3
+    if rank == 0:
+        dump_outputs(args, {"y": (y, 0), "attempts": steps})
+    data = "synthetic: irregular grids T_p ~ U{20..60} on [0,10], EQ_4_C statics, random per-interval arms"
+    workload = f"C5: adaptive RK45 (rtol=atol=1.4e-8) on irregular grids, {N_total // 1000}k patients"
+    if not args.full:
+        if rank == 0:
+            emit(headline(args, N_total / (ms_step * 1e-3), ms_step, world, "strong", "f64", data, workload))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # per-launch duration with HIP events on the launch stream (instrumented pass after the timed region)
     st_ = torch.cuda.current_stream(dev)
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(max(args.steps, 5))]
@@ -686,10 +750,8 @@ def c5_main(args):
     out = {
         "metric": METRIC, "value": N_total / (ms_step * 1e-3), "unit": "patient-trajectories/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None, "dtype": "f64",
-        "data": "synthetic: irregular grids T_p ~ U{20..60} on [0,10], EQ_4_C statics, random per-interval arms",
-        "config": {"workload": f"C5: adaptive RK45 (rtol=atol=1.4e-8) on irregular grids, {N_total // 1000}k patients",
-                   "patients_total": N_total, "patients_per_gpu": N, "max_obs": Tm,
+        "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": data,
+        "config": {"workload": workload, "patients_total": N_total, "patients_per_gpu": N, "max_obs": Tm,
                    "mean_intervals": float(intervals.mean()), "parallelism": f"patient-shard x{world}"},
         "roofline": {"kernel": "rollout_rk45_kernel", "bound": "valu-f64", "unit": "TFLOP/s",
                      "achieved": flop / (launch_ms * 1e-3) / 1e12, "peak": FP64_VALU_PEAK_TFLOPS,
@@ -1160,6 +1222,11 @@ def insite_main(args):
     ms_identity, _ = (None, None) if only else timed("identity")
     ms_prepare, prep_out = (None, None) if only else timed("prepare")
     ms_step, (preds, coef, status, iters) = timed("binned")    # the product default: rows binned by seq_len
+    dump_outputs(args, {"preds": (preds, 0), "coef": (coef, 0), "status": (status, 0), "iters": (iters, 0)})
+    data = "synthetic: on-device EQ_4_C cohort, T=60, seq_len U{1..59}, arm flip at a random step"
+    workload = f"INSITE refinement (BFGS per row, tau=5, lam=10) + Euler-5 rollout, {N // 1000}k rows"
+    if not args.full:
+        return emit(headline(args, N / (ms_step * 1e-3), ms_step, 1, "weak", "f64", data, workload))
     eager = ops.insite_refine(V, arm, coh.u, sl, c0, coh.lib, dt, 10.0, 5, binned=True)
     plan_eq = all(bool(torch.equal(a, b)) for a, b in zip(eager, (preds, coef, status, iters)))
     prep_eq = None if only else all(bool(torch.equal(a, b)) for a, b in zip(prep_out, (preds, coef, status, iters)))
@@ -1219,10 +1286,8 @@ def insite_main(args):
     out = {
         "metric": METRIC, "value": N / (ms_step * 1e-3), "unit": "patient-trajectories/s", "n_gpus": 1,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f64",
-        "data": "synthetic: on-device EQ_4_C cohort, T=60, seq_len U{1..59}, arm flip at a random step",
-        "config": {"workload": f"INSITE refinement (BFGS per row, tau=5, lam=10) + Euler-5 rollout, "
-                               f"{N // 1000}k rows", "rows": N, "T": T},
+        "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": data,
+        "config": {"workload": workload, "rows": N, "T": T},
         "insite": {"refined_rows": int((st >= 0).sum()), "converged": int((st == 0).sum()),
                    "zoom_failed_fallback": int((st == 3).sum()), "mean_bfgs_iterations": float(it[st >= 0].mean()),
                    "lane_order": ("rows binned by seq_len (device counting sort)" if args.insite_order == "seq_len"
@@ -1410,7 +1475,13 @@ def insite4_main(args):
     models = _insite4_models(V, arm, u, dt, lib)
     st_ = torch.cuda.current_stream(dev)
     res = {}
+    data = ("synthetic: on-device 4-arm cohort (F4's planted model, Markov arms, Euler-5 truth + 0.01 noise), "
+            "T=60, seq_len U{1..59}")
+    workload = (f"INSITE refinement, 4 arms (cancer_sim / EQ_5 path; BFGS per row, tau=5, lam=10) + "
+                f"Euler-5 rollout, {N // 1000}k rows; value = the dense per-arm model")
     for name, (c0, lb) in models.items():
+        if not args.full and name != "dense":    # the line's value is the dense model's step
+            continue
         plan = ops.plan_insite_refine(V, arm, u, sl, c0, lb, dt, 10.0, 5, order=args.insite_order)
         for _ in range(args.warmup):
             plan()
@@ -1420,6 +1491,10 @@ def insite4_main(args):
             preds, coef, status, iters = plan()
         torch.cuda.synchronize(dev)
         ms = (time.perf_counter() - t0) / args.steps * 1e3
+        if name == "dense":
+            dump_outputs(args, {"preds": (preds, 0), "coef": (coef, 0), "status": (status, 0), "iters": (iters, 0)})
+        if not args.full:
+            return emit(headline(args, N / (ms * 1e-3), ms, 1, "weak", "f64", data, workload))
         kidx = plan.kernel_call                  # [(key,) sort, prepare, kernel, finish(, nfev scatter)]
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(st_)
@@ -1465,12 +1540,8 @@ def insite4_main(args):
     out = {
         "metric": METRIC, "value": N / (d["ms_per_step"] * 1e-3), "unit": "patient-trajectories/s", "n_gpus": 1,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": d["ms_per_step"], "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f64",
-        "data": "synthetic: on-device 4-arm cohort (F4's planted model, Markov arms, Euler-5 truth + 0.01 noise), "
-                "T=60, seq_len U{1..59}",
-        "config": {"workload": f"INSITE refinement, 4 arms (cancer_sim / EQ_5 path; BFGS per row, tau=5, lam=10) + "
-                               f"Euler-5 rollout, {N // 1000}k rows; value = the dense per-arm model", "rows": N,
-                   "T": T, "arms": 4},
+        "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": data,
+        "config": {"workload": workload, "rows": N, "T": T, "arms": 4},
         "models": res,
         "roofline": {"kernel": d["kernel"] + " (dense per-arm model: 8 lanes per row, H rows in VGPRs)",
                      "bound": "valu-f64", "unit": "TFLOP/s", "achieved": d["valu_f64_TFLOPs"],
@@ -1534,6 +1605,12 @@ def f4_main(args):
         step(st)
     torch.cuda.synchronize(dev)
     ms_step = (time.perf_counter() - t0) / args.steps * 1e3
+    dump_outputs(args, {"coef": out[0], "mask": out[1], "iters": out[2], "G": out[3], "b": out[4], "y": (y, 1)})
+    data = "synthetic: on-device 4-arm cohort (planted per-arm model, Markov arms p=0.1, Euler-5 truth + 0.01 noise)"
+    workload = (f"F4: cancer_sim/EQ_5 path, {N // 1000}k patients x {T} steps, 4 arms: segment-split "
+                f"FD1 discovery + STLSQ (threshold 0.001) + Euler-5 4-arm counterfactual rollout")
+    if not args.full:
+        return emit(headline(args, N / (ms_step * 1e-3), ms_step, 1, "weak", "f64", data, workload))
 
     def timed(fn, n):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -1553,11 +1630,8 @@ def f4_main(args):
     res = {
         "metric": METRIC, "value": N / (ms_step * 1e-3), "unit": "patient-trajectories/s", "n_gpus": 1,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f64",
-        "data": "synthetic: on-device 4-arm cohort (planted per-arm model, Markov arms p=0.1, Euler-5 truth + 0.01 noise)",
-        "config": {"workload": f"F4: cancer_sim/EQ_5 path, {N // 1000}k patients x {T} steps, 4 arms: segment-split "
-                               f"FD1 discovery + STLSQ (threshold 0.001) + Euler-5 4-arm counterfactual rollout",
-                   "patients": N, "T": T, "arms": 4, "library_terms": F,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": data,
+        "config": {"workload": workload, "patients": N, "T": T, "arms": 4, "library_terms": F,
                    "discovered_support": (out[1].cpu().numpy() != 0).astype(int).tolist(),
                    # recovery check of the planted model: with the reference's cancer_sim / EQ_5 threshold
                    # (0.001, config/config.yaml:20-23) the first-order FD bias and the 0.01 observation noise
@@ -1693,6 +1767,20 @@ def c4_main(args):
         dist.barrier()
     el = idist.max_over_ranks(time.perf_counter() - t0, dev)
     ms_step = el / args.steps * 1e3
+    if rank == 0:
+        dump_outputs(args, {"coef": gout[0], "mask": gout[1], "iters": gout[2], "G": buf.G, "b": buf.b,
+                            "moments": (mom, 0), "y": (y, 1)})
+    data = "synthetic: on-device EQ_4_C PK/PD cohort (reference distributions, Euler-5 truth + 0.01 noise)"
+    workload = (f"C4: PK/PD {N_total // 1000}k patients x {T} steps: global discovery and every "
+                f"patient's moments in one pass (+ RCCL all-reduce when N>1) + per-patient STLSQ "
+                f"folded into the per-patient-coefficient Euler-5 rollout")
+    if not args.full:
+        if rank == 0:
+            emit(headline(args, N_total / (ms_step * 1e-3), ms_step, world, "strong", "f64", data, workload))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     st = torch.cuda.current_stream(dev)
 
     def timed(fn, n):
@@ -1722,11 +1810,8 @@ def c4_main(args):
         res = {
             "metric": METRIC, "value": N_total / (ms_step * 1e-3), "unit": "patient-trajectories/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic: on-device EQ_4_C PK/PD cohort (reference distributions, Euler-5 truth + 0.01 noise)",
-            "config": {"workload": f"C4: PK/PD {N_total // 1000}k patients x {T} steps: global discovery and every "
-                                   f"patient's moments in one pass (+ RCCL all-reduce when N>1) + per-patient STLSQ "
-                                   f"folded into the per-patient-coefficient Euler-5 rollout", "patients_total": N_total, "patients_per_gpu": N, "T": T,
+            "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": data,
+            "config": {"workload": workload, "patients_total": N_total, "patients_per_gpu": N, "T": T,
                        "parallelism": f"patient-shard x{world}",
                        "global_support": (gout[1].cpu().numpy() != 0).astype(int).tolist(),
                        "mean_per_patient_iterations": float(it.mean())},
@@ -1998,6 +2083,13 @@ def fused_run(args, dev, coh, arm_cf, coh2=None, arm_cf2=None):
     torch.cuda.synchronize(dev)
     ms_step = (time.perf_counter() - t0) / args.steps * 1e3
     last = (args.steps - 1) % 2
+    # the last launch discovered cohort ``last`` and rolled the other cohort out with the other buffer's model
+    dump_outputs(args, {"coef": coefs[last], "mask": masks[last], "iters": iters[last], "G": Gs[last], "b": bs[last],
+                        "rollout_coef": coefs[1 - last], "y": (ys[1 - last], 1)})
+    res = {"ms_step": ms_step, "host_ms": host_ms, "coef": coefs[last], "mask": masks[last], "y": ys[last],
+           "rotated": coh2 is not None}
+    if not args.full:
+        return res
     # instrumented pass: HIP timing events on the launch stream around batches of KB back-to-back launches
     # (an event record costs ~20 us of queue time on ROCm 7.2, so never one per launch), divided by KB
     hip = HipEvents()
@@ -2013,9 +2105,8 @@ def fused_run(args, dev, coh, arm_cf, coh2=None, arm_cf2=None):
     torch.cuda.synchronize(dev)
     step_ms = float(np.mean([hip.elapsed_ms(e0, e1) for e0, e1 in tevs])) / KB
     rb, gb = rollout_bytes(N, T, arm_bits=1), gram_bytes(N, T)
-    return {"ms_step": ms_step, "host_ms": host_ms, "step_ms": step_ms, "KB": KB, "NBAT": NBAT,
-            "coef": coefs[last], "mask": masks[last], "y": ys[last], "rb": rb, "gb": gb, "rotated": coh2 is not None,
-            "frac": (rb + gb) / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS}
+    return dict(res, step_ms=step_ms, KB=KB, NBAT=NBAT, rb=rb, gb=gb,
+                frac=(rb + gb) / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS)
 
 
 def deferred_run(args, dev, coh, arm_cf, coh2=None, arm_cf2=None):
@@ -2083,6 +2174,23 @@ def deferred_run(args, dev, coh, arm_cf, coh2=None, arm_cf2=None):
     host_ms = (time.perf_counter() - t0) / args.steps * 1e3
     torch.cuda.synchronize(dev)
     ms_step = (time.perf_counter() - t0) / args.steps * 1e3
+
+    def last_launch():
+        """What the latest launch wrote and used."""
+        mine, outs, ys, _ = lanes[(turn[0] - 1) % S]
+        last = pos[(turn[0] - 1) % S] - 1
+        # it finalised the model of the previous launch's cohort, and rolled cohort mine[last % m] out with the model
+        # finalised one launch earlier -- that of the same data cohort two launches back (m = 2): the bench line's
+        # parity check compares THAT model and y
+        return {"fin": outs[(last - 1) % 3], "y": ys[last % len(mine)], "used": outs[(last - 2) % 3],
+                "roll_cohort": mine[last % len(mine)]}
+
+    ll = last_launch()
+    dump_outputs(args, {**dict(zip(("coef", "mask", "iters", "G", "b"), ll["fin"])), "rollout_coef": ll["used"][0],
+                        "y": (ll["y"], 1)})
+    res = {"ms_step": ms_step, "host_ms": host_ms, "rotated": coh2 is not None, "streams": S}
+    if not args.full:
+        return dict(res, coef=ll["fin"][0], mask=ll["fin"][1], y=ll["y"])
     # instrumented pass: timing events on stream 0 around batches of KB steps; the other streams' last launches
     # are joined into stream 0 before the closing event (one ordering event per stream per batch)
     hip = HipEvents()
@@ -2105,16 +2213,10 @@ def deferred_run(args, dev, coh, arm_cf, coh2=None, arm_cf2=None):
     torch.cuda.synchronize(dev)
     step_ms = float(np.mean([hip.elapsed_ms(e0, e1) for e0, e1 in tevs])) / KB
     rb, gb = rollout_bytes(N, T, arm_bits=1), gram_bytes(N, T)
-    mine, outs, ys, _ = lanes[(turn[0] - 1) % S]
-    last = pos[(turn[0] - 1) % S] - 1
-    fin = outs[(last - 1) % 3]
-    # the last launch rolled cohort mine[last % m] out with the model finalised one launch earlier -- that of the
-    # same data cohort two launches back (m = 2): the bench line's parity check compares THAT model and y
-    used = outs[(last - 2) % 3]
-    return {"ms_step": ms_step, "host_ms": host_ms, "step_ms": step_ms, "KB": KB, "NBAT": NBAT,
-            "coef": fin[0], "mask": fin[1], "y": ys[last % len(mine)], "rb": rb, "gb": gb, "rotated": coh2 is not None,
-            "streams": S, "frac": (rb + gb) / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-            "roll_coef": used[0], "roll_mask": used[1], "roll_cohort": mine[last % len(mine)]}
+    ll = last_launch()
+    return dict(res, step_ms=step_ms, KB=KB, NBAT=NBAT, coef=ll["fin"][0], mask=ll["fin"][1], y=ll["y"], rb=rb, gb=gb,
+                frac=(rb + gb) / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                roll_coef=ll["used"][0], roll_mask=ll["used"][1], roll_cohort=ll["roll_cohort"])
 
 
 def c2_parity(dev, coh, arm_bits, coef, mask, y, n_sample=4096, seed=11, pooled=False):
@@ -2185,6 +2287,13 @@ def c2_fused(args, dev, coh, arm_cf, cpu):
                                              layout=bits_layout(args.arm_format))
     deferred = args.mode == "deferred"
     fr = (deferred_run if deferred else fused_run)(args, dev, coh, arm_cf, coh2, arm_cf2)
+    data = "synthetic: on-device EQ_4_C PK/PD cohort (reference distributions, Euler-5 truth + 0.01 noise)"
+    workload = (f"C2: PK/PD {N // 1000}k patients/GPU x {T} steps fp64 - discovery (savgol+FD4+poly2 "
+                f"library+Gram, STLSQ) + {args.method.upper()} counterfactual rollout")
+    if not args.full:
+        line = headline(args, N / (fr["ms_step"] * 1e-3), fr["ms_step"], 1, "weak", "f64", data, workload)
+        line["config"]["mode"] = args.mode
+        return emit(line)
     ms_step, host_ms, step_ms, KB, NBAT = fr["ms_step"], fr["host_ms"], fr["step_ms"], fr["KB"], fr["NBAT"]
     y = fr["y"]
     st = torch.cuda.current_stream(dev)
@@ -2226,10 +2335,9 @@ def c2_fused(args, dev, coh, arm_cf, cpu):
         "scaling": "weak",
         "vs_baseline": None,
         "dtype": "f64",
-        "data": "synthetic: on-device EQ_4_C PK/PD cohort (reference distributions, Euler-5 truth + 0.01 noise)",
+        "data": data,
         "config": {
-            "workload": f"C2: PK/PD {N // 1000}k patients/GPU x {T} steps fp64 - discovery (savgol+FD4+poly2 "
-                        f"library+Gram, STLSQ) + {args.method.upper()} counterfactual rollout",
+            "workload": workload,
             "patients_per_gpu": N, "T": T, "rows_per_patient": T - 2, "library_terms": F,
             "parallelism": "patient-shard x1", "mode": args.mode, "gram_blocks": args.gram_blocks or "default",
             "discovered_support": sup.tolist(), "finite": ok,
@@ -2395,7 +2503,19 @@ def c2_lagged(args, dev, world, rank, coh, arm_cf, cpu, collective):
         dist.barrier()
     el = idist.max_over_ranks(time.perf_counter() - t0, dev)
     ms_step = el / args.steps * 1e3
-    last = kk[0] - 1
+    p_last = sched.launch(kk[0] - 1)
+    if rank == 0:   # the last launch: the model it solved (if its slot of the schedule had one), its rollout and its model
+        rc_, r = p_last["rollout"]
+        dump_outputs(args, {**(dict(zip(("coef", "mask", "iters"), ring[p_last["fit"][3]])) if p_last["fit"] else {}),
+                            "rollout_coef": ring[r][0], "rollout_mask": ring[r][1], "y": (ys[rc_ % 2], 1)})
+    data = "synthetic: on-device EQ_4_C PK/PD cohorts (reference distributions, Euler-5 truth + 0.01 noise)"
+    workload = (f"C2: PK/PD {N // 1000}k patients/GPU x {T} steps fp64 - discovery (savgol+FD4+poly2 "
+                f"library+Gram, one RCCL all-reduce per {K} fits, STLSQ) + {args.method.upper()} "
+                "counterfactual rollout")
+    if not args.full:
+        line = headline(args, N * world / (ms_step * 1e-3), ms_step, world, "weak", "f64", data, workload)
+        line["config"]["mode"] = "lagged"
+        return (line if rank == 0 else None), None
     # instrumented pass: HIP events around batches of KB launches (+ their collectives), divided by KB
     hip = HipEvents()
     KB, NBAT = max(args.steps // K * K, 2 * K), 3
@@ -2427,11 +2547,9 @@ def c2_lagged(args, dev, world, rank, coh, arm_cf, cpu, collective):
             "scaling": "weak",
             "vs_baseline": None,
             "dtype": "f64",
-            "data": "synthetic: on-device EQ_4_C PK/PD cohorts (reference distributions, Euler-5 truth + 0.01 noise)",
+            "data": data,
             "config": {
-                "workload": f"C2: PK/PD {N // 1000}k patients/GPU x {T} steps fp64 - discovery (savgol+FD4+poly2 "
-                            f"library+Gram, one RCCL all-reduce per {K} fits, STLSQ) + {args.method.upper()} "
-                            "counterfactual rollout",
+                "workload": workload,
                 "patients_per_gpu": N, "T": T, "rows_per_patient": T - 2, "library_terms": F,
                 "parallelism": f"patient-shard x{world}" + (" (single-rank RCCL group: --force-collective)"
                                                              if args.force_collective and world == 1 else ""),
@@ -2472,17 +2590,22 @@ def north_star_step(args, dev):
     from insite_amd import cohort
     ns = argparse.Namespace(**vars(args))
     ns.patients, ns.T, ns.steps, ns.warmup, ns.dstreams, ns.gram_blocks = 1_000_000, 500, max(2, args.ns_steps), 3, 1, 0
+    if args.config != "ns":     # a block of the C2 line: --dump-outputs holds that line's own outputs
+        ns.dump_outputs = None
     N, T = ns.patients, ns.T
     sd = [args.seed * 1000 + 900, args.seed * 1000 + 901]
     cohs = [cohort.synthetic_pkpd(N, T, seed=s_, device=dev, equation="EQ_4_C", layout="time") for s_ in sd]
     arms = [cohort.counterfactual_arms(c.arm, T, seed=s_, layout=bits_layout(args.ns_arms)) for c, s_ in zip(cohs, sd)]
     torch.cuda.synchronize(dev)
     fr = deferred_run(ns, dev, cohs[0], arms[0], cohs[1], arms[1])
-    rb, gb = fr["rb"], fr["gb"]
     out = {"workload": "north star: PK/PD EQ_4_C 1M patients x 500 steps fp64 - discovery (savgol+FD4+poly2 "
                        "library+Gram, STLSQ) + RK4 counterfactual rollout, one step_deferred_kernel launch per step",
            "patients": N, "T": T, "steps": ns.steps, "warmup": ns.warmup, "cohorts_rotated": 2,
-           "ms_per_step": fr["ms_step"], "patient_trajectories_per_s": N / (fr["ms_step"] * 1e-3),
+           "ms_per_step": fr["ms_step"], "patient_trajectories_per_s": N / (fr["ms_step"] * 1e-3)}
+    if not args.full:           # --config ns without --full: the timed launches alone
+        return out
+    rb, gb = fr["rb"], fr["gb"]
+    out = {**out,
            "discovered_support": fr["mask"].cpu().numpy().tolist(),
            "finite": bool(torch.isfinite(fr["y"]).all().item()),
            "roofline": {"kernel": "step_deferred_kernel<true, rk4>", "bound": "hbm", "peak": HBM_PEAK_GBPS,
@@ -2617,9 +2740,10 @@ def main():
     if args.mode in ("fused", "deferred"):
         return c2_fused(args, dev, coh, arm_cf, cpu)
     if args.mode == "lagged":
-        out, (rcoh, rcoef, rmask, ry) = c2_lagged(args, dev, world, rank, coh, arm_cf, cpu, collective)
+        out, used = c2_lagged(args, dev, world, rank, coh, arm_cf, cpu, collective)
         if out is not None:
             if not args.no_parity:
+                rcoh, rcoef, rmask, ry = used
                 out["parity"] = c2_parity(dev, rcoh[0], rcoh[1], rcoef, rmask, ry) if world == 1 else {
                     "skipped": "N > 1: each rank's model is the all-rank fit; the single-rank parity is tests/"
                                "test_gpu_deferred.py and test_dist.py::test_lagged_schedule_gloo_world2"}
@@ -2799,6 +2923,22 @@ def main():
     ms_step = el / args.steps * 1e3
     coef = coefs[0] if mode == "graph" else coefs[(args.steps - 1) % NB]
     mask = masks[0] if mode == "graph" else masks[(args.steps - 1) % NB]
+    jl = 0 if mode == "graph" else (args.steps - 1) % NB      # the last timed step's buffers
+    if rank == 0:
+        dump_outputs(args, {"coef": coef, "mask": mask, "iters": iters[jl], "G": bufs[jl].G, "b": bufs[jl].b,
+                            "y": (ys[(jl // K) % RS], 0 if args.layout == "patient" else 1)})
+    data = "synthetic: on-device EQ_4_C PK/PD cohort (reference distributions, Euler-5 truth + 0.01 noise)"
+    workload = (f"C2: PK/PD {N // 1000}k patients/GPU x {T} steps fp64 - discovery (savgol+FD4+poly2 "
+                f"library+Gram, RCCL all-reduce when N>1, STLSQ) + {args.method.upper()} counterfactual rollout")
+    if not args.full:
+        if rank == 0:
+            line = headline(args, N * world / (ms_step * 1e-3), ms_step, world, "weak", "f64", data, workload)
+            line["config"]["mode"] = mode
+            emit(line)
+        if dist.is_available() and dist.is_initialized():
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # instrumented pass (after the timed region): the same schedule again — same streams, same overlap —
     # with HIP timing events around the gram and rollout launches on the streams they run on.  Per-launch
@@ -2868,10 +3008,9 @@ def main():
             "scaling": "weak",
             "vs_baseline": None,
             "dtype": "f64",
-            "data": "synthetic: on-device EQ_4_C PK/PD cohort (reference distributions, Euler-5 truth + 0.01 noise)",
+            "data": data,
             "config": {
-                "workload": f"C2: PK/PD {N // 1000}k patients/GPU x {T} steps fp64 - discovery (savgol+FD4+poly2 "
-                            f"library+Gram, RCCL all-reduce when N>1, STLSQ) + {args.method.upper()} counterfactual rollout",
+                "workload": workload,
                 "patients_per_gpu": N, "T": T, "rows_per_patient": T - 2, "library_terms": F,
                 "parallelism": f"patient-shard x{world}" + (" (single-rank RCCL group: --force-collective)"
                                                              if args.force_collective and world == 1 else ""),
@@ -2947,7 +3086,7 @@ def main():
     # the same step as ONE fused launch (step_kernel, insite_fit_rollout_f64), measured beside the headline
     if rank == 0 and world == 1 and mode == "pipeline" and not args.no_fused:
         try:
-            fr = fused_run(args, dev, coh, arm_cf)
+            fr = fused_run(argparse.Namespace(**{**vars(args), "dump_outputs": None}), dev, coh, arm_cf)
         except Exception as exc:  # a secondary measurement never costs the headline line
             fr = None
             out["fused_step_kernel"] = {"error": f"{type(exc).__name__}: {exc}"}
