@@ -29,6 +29,7 @@
 #include <cstring>
 
 #include "insite_hip.h"
+#include "insite_irregular.h"
 #include "insite_common.h"
 
 namespace {
@@ -1613,6 +1614,249 @@ gram_seg_kernel(const double* __restrict__ x, int64_t xsp, int64_t xsk, const in
     tail_store(partial + (int64_t)blockIdx.x * n_ent + idx, sum);
   }
   gram_tail<STF>((int)blockIdx.x, (int)gridDim.x, partial, n_ent, cnt, lib, out, smem);
+}
+
+// =============================================================================================
+// Discovery on irregular observation grids (insite_irregular.h)
+// =============================================================================================
+// Every patient has its own strictly increasing times t[0 .. L), L = n_obs[p] (C5's shape: x / t_obs
+// [N, ld] patient-major, padding past L arbitrary).  x_dot at sample k is the derivative at t_k of the
+// Lagrange interpolant through the W consecutive samples [lo, lo + W), lo = clamp(k - W/2, 0, L - W): W = 3 is
+// numpy.gradient(x, t, edge_order=2) = pysindy FiniteDifference(order=2, is_uniform=False), W = 5 its
+// five-point form.  Patients with L < W contribute nothing; the library sees the raw samples.
+// Streaming form, lane = patient, one 64-patient tile per wave at a time: tiles of kGT steps of x and of t are
+// loaded coalesced (the next pair in flight while the current one is consumed) and staged through the wave's two
+// LDS slots; each lane slides a W-sample window over its own row.  The window keeps the reciprocals of its
+// W(W-1)/2 node differences, so a step costs W - 1 new reciprocals (v_rcp_f64 + two Newton steps; an IEEE
+// division is ~3x that), and every weight is a product of differences and stored reciprocals.  When sample j
+// arrives the window [j - W + 1, j] is complete: its centre k = j - W/2 is an interior sample (or the centre
+// of a window of an L = W patient); at j = W - 1 (wave-uniform) the window also serves the W/2 head samples.
+// The W/2 tail samples use the patient's last window, which the lane snapshots when j = L - 1 and evaluates once
+// after the time loop -- lanes end at different steps, and evaluating the shifted stencils inside the loop
+// would run them at almost every step of a ragged tile.  Samples past a lane's L enter its window (they may be
+// NaN) but reach an accumulator only through a select.  Per tile the lane's moments {L, sum x, sum x^2,
+// sum xdot, sum xdot x} are expanded per arm as in gram_body's scalar path (one Gram entry per lane), the block
+// partial is gram_block_partial's and the in-launch fixed-order reduction (+ STLSQ, STF > 0) gram_tail's.
+template <int W>
+struct IrrWin {
+  double t[W], x[W];
+  double r[W][W];  // r[a][b], a > b: 1 / (t[a] - t[b])
+};
+
+__device__ __forceinline__ double irr_rcp(double d) {
+  double r = __builtin_amdgcn_rcp(d);
+  r = fma(fma(-d, r, 1.0), r, r);
+  r = fma(fma(-d, r, 1.0), r, r);
+  return r;
+}
+
+template <int W>
+__device__ __forceinline__ void irr_push(IrrWin<W>& w, double tn, double xn) {
+#pragma unroll
+  for (int a = 0; a < W - 1; ++a) {
+    w.t[a] = w.t[a + 1];
+    w.x[a] = w.x[a + 1];
+  }
+#pragma unroll
+  for (int a = 1; a < W - 1; ++a)
+#pragma unroll
+    for (int b = 0; b < a; ++b) w.r[a][b] = w.r[a + 1][b + 1];
+  w.t[W - 1] = tn;
+  w.x[W - 1] = xn;
+#pragma unroll
+  for (int b = 0; b < W - 1; ++b) w.r[W - 1][b] = irr_rcp(tn - w.t[b]);
+}
+
+// d/dt of the window's Lagrange interpolant at its node K: weight of x_j (j != K) =
+// prod_{m != j, K} (t_K - t_m) / (t_j - t_m) / (t_j - t_K); weight of x_K = sum_{m != K} 1 / (t_K - t_m)
+template <int W, int K>
+__device__ __forceinline__ double irr_deriv(const IrrWin<W>& w) {
+  double d[W];  // t_K - t_m
+#pragma unroll
+  for (int m = 0; m < W; ++m) d[m] = w.t[K] - w.t[m];
+  double wk = 0.0;
+#pragma unroll
+  for (int m = 0; m < W; ++m)
+    if (m != K) wk += m < K ? w.r[K][m] : -w.r[m][K];
+  double acc = wk * w.x[K];
+#pragma unroll
+  for (int j = 0; j < W; ++j) {
+    if (j == K) continue;
+    double c = j > K ? w.r[j][K] : -w.r[K][j];
+#pragma unroll
+    for (int m = 0; m < W; ++m) {
+      if (m == j || m == K) continue;
+      c *= d[m] * (j > m ? w.r[j][m] : -w.r[m][j]);
+    }
+    acc = fma(c, w.x[j], acc);
+  }
+  return acc;
+}
+
+template <int W, int K0, int K1>
+__device__ __forceinline__ void irr_edge(const IrrWin<W>& w, bool on, double& Sx, double& Sxx, double& Sd,
+                                         double& Sdx) {  // nodes [K0, K1) of the window
+  if constexpr (K0 < K1) {
+    const double dk = irr_deriv<W, K0>(w);
+    add_row(on ? w.x[K0] : 0.0, on ? dk : 0.0, Sx, Sxx, Sd, Sdx);
+    irr_edge<W, K0 + 1, K1>(w, on, Sx, Sxx, Sd, Sdx);
+  }
+}
+
+constexpr int kIrrSmem = 2 * kWavesPerBlock * kWave * kGSlot;  // doubles: an x and a t slot per wave
+template <int W, int VEC, int NARM, int STF>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2)))
+gram_irr_kernel(const double* __restrict__ x, int64_t ldx, const double* __restrict__ tobs, int64_t ldt,
+                const int32_t* __restrict__ n_obs, const double* __restrict__ u, const int8_t* __restrict__ arm,
+                int64_t N, int T_max, LibDesc lib, double* __restrict__ partial, unsigned* __restrict__ cnt,
+                GramOut out) {
+  __shared__ double smem[kIrrSmem];
+  static_assert(kIrrSmem >= kGramSmem, "gram_tail's scratch fits");
+  constexpr int C = W / 2;
+  constexpr int LPR = kGT / VEC;    // lanes per row segment
+  constexpr int RPI = kWave / LPR;  // rows per wave instruction
+  constexpr int NLD = kWave / RPI;  // load instructions per tile and array
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  double* xt = smem + wid * (2 * kWave * kGSlot);
+  double* tt = xt + kWave * kGSlot;
+  const dbl4 cacc = {0.0, 0.0, 0.0, 0.0};  // (gram_block_partial's MFMA operand: unused)
+  double acc[NARM];
+#pragma unroll
+  for (int a = 0; a < NARM; ++a) acc[a] = 0.0;
+  const int my_i = lane < lib.nE ? lib.ei[lane] : 0;
+  const int my_k = lane < lib.nE ? lib.ek[lane] : 0;
+  const int my_exi = lib.ex[my_i];
+  const int my_exk = my_k >= 0 ? lib.ex[my_k] : 0;
+  const int cl = (lane % LPR) * VEC;
+
+  const int64_t n_tiles = (N + kWave - 1) / kWave;
+  const int64_t nW = (int64_t)gridDim.x * kWavesPerBlock;
+  for (int64_t tile = (int64_t)blockIdx.x * kWavesPerBlock + wid; tile < n_tiles; tile += nW) {
+    const int64_t p0 = tile * kWave;
+    const int64_t p = p0 + lane;
+    const int64_t pcl = p < N ? p : N - 1;
+    int L = n_obs[pcl];
+    const int arm_p = arm[pcl];
+    double uu[INSITE_MAX_STATICS];
+#pragma unroll
+    for (int t = 0; t < INSITE_MAX_STATICS; ++t) uu[t] = u[pcl * lib.U + (t < lib.U ? t : 0)];
+    if (L > T_max) L = T_max;
+    if (p >= N || L < W) L = 0;
+    const int Lmax = wave_max_i(L);  // tiles past it are not loaded
+
+    typedef double TileRegs[NLD][VEC];
+    TileRegs vx, vt;
+    // Issued unconditionally from a clamped (always valid) address; what is past a lane's L is masked at the use.
+    // Every row is read up to the wave's longest patient: pointing the segments past a row's own samples at an
+    // already cached line (~20 % fewer HBM bytes on C5's lengths) measured 2-5 % slower.
+    auto load_tile = [&](int t0) {
+      const int col = t0 + cl;
+      const int colc = col < Lmax ? col : 0;
+#pragma unroll
+      for (int it = 0; it < NLD; ++it) {
+        const int64_t pr = p0 + it * RPI + lane / LPR;
+        const int64_t prc = pr < N ? pr : N - 1;
+        const double* sx = x + prc * ldx + colc;
+        const double* st = tobs + prc * ldt + colc;
+        if constexpr (VEC == 2) {
+          const double2 qx = *reinterpret_cast<const double2*>(sx);
+          const double2 qt = *reinterpret_cast<const double2*>(st);
+          vx[it][0] = qx.x;
+          vx[it][1] = qx.y;
+          vt[it][0] = qt.x;
+          vt[it][1] = qt.y;
+        } else {
+          vx[it][0] = *sx;
+          vt[it][0] = *st;
+        }
+      }
+    };
+    auto store_tile = [&]() {
+      wave_lds_sync();  // every lane finished reading the previous tile
+#pragma unroll
+      for (int it = 0; it < NLD; ++it) {
+        const int r = it * RPI + lane / LPR;
+#pragma unroll
+        for (int q = 0; q < VEC; ++q) {
+          xt[r * kGStride + cl + q] = vx[it][q];
+          tt[r * kGStride + cl + q] = vt[it][q];
+        }
+      }
+      wave_lds_sync();
+    };
+
+    double Sx = 0.0, Sxx = 0.0, Sd = 0.0, Sdx = 0.0;
+    IrrWin<W> win, fin;  // the sliding window; the lane's last window (snapshot at j = L - 1)
+#pragma unroll
+    for (int a = 0; a < W; ++a) {
+      win.t[a] = win.x[a] = fin.t[a] = fin.x[a] = 0.0;
+#pragma unroll
+      for (int b = 0; b < a; ++b) win.r[a][b] = 0.0;
+    }
+    if (Lmax > 0) load_tile(0);
+    for (int t0 = 0; t0 < Lmax; t0 += kGT) {
+      store_tile();
+      if (t0 + kGT < Lmax) load_tile(t0 + kGT);
+#pragma unroll
+      for (int i = 0; i < kGT; ++i) {
+        const int j = t0 + i;
+        irr_push<W>(win, tt[lane * kGStride + i], xt[lane * kGStride + i]);
+        const bool on = j >= W - 1 && j < L;
+        const double dk = irr_deriv<W, C>(win);
+        add_row(on ? win.x[C] : 0.0, on ? dk : 0.0, Sx, Sxx, Sd, Sdx);
+        if (i == W - 1 && t0 == 0) irr_edge<W, 0, C>(win, L > 0, Sx, Sxx, Sd, Sdx);  // head samples (uniform)
+        if (j == L - 1) {
+#pragma unroll
+          for (int a = 0; a < W; ++a) {
+            fin.t[a] = win.t[a];
+            fin.x[a] = win.x[a];
+          }
+        }
+      }
+    }
+    if (Lmax > 0) {  // tail samples from the last window
+#pragma unroll
+      for (int a = 1; a < W; ++a)
+#pragma unroll
+        for (int b = 0; b < a; ++b) fin.r[a][b] = irr_rcp(fin.t[a] - fin.t[b]);
+      irr_edge<W, C + 1, W>(fin, L > 0, Sx, Sxx, Sd, Sdx);
+    }
+    if (out.mom && p < N) {
+      double* mrow = out.mom + p * 5;
+      mrow[0] = (double)L;
+      mrow[1] = Sx;
+      mrow[2] = Sxx;
+      mrow[3] = Sd;
+      mrow[4] = Sdx;
+    }
+    if (Lmax == 0) continue;  // (uniform) nothing to add
+    // ---- per-patient Gram block A(u) M A(u)^T, one entry per lane (gram_body's scalar path) ----
+    double* ps = xt;
+    wave_lds_sync();
+    for (int j = 0; j < lib.F; ++j) ps[lane * kPsStride + j] = monomial(lib, j, uu);
+    ps[lane * kPsStride + 9] = (double)L;
+    ps[lane * kPsStride + 10] = Sx;
+    ps[lane * kPsStride + 11] = Sxx;
+    ps[lane * kPsStride + 12] = Sd;
+    ps[lane * kPsStride + 13] = Sdx;
+    ps[lane * kPsStride + 14] = (double)(L > 0 ? arm_p : -1);
+    wave_lds_sync();
+    if (lane < lib.nE) {
+      const int moff = my_k >= 0 ? 9 + my_exi + my_exk : 12 + my_exi;
+      for (int q = 0; q < kWave; ++q) {
+        const double* row = ps + q * kPsStride;
+        double wq = row[my_i] * row[moff];
+        if (my_k >= 0) wq *= row[my_k];
+        const int a = (int)row[14];
+#pragma unroll
+        for (int aa = 0; aa < NARM; ++aa) acc[aa] += (a == aa) ? wq : 0.0;
+      }
+    }
+    wave_lds_sync();
+  }
+  gram_block_partial<false, NARM>((int)blockIdx.x, smem, lib, out, partial, cacc, acc, wid, lane);
+  gram_tail<STF>((int)blockIdx.x, (int)gridDim.x, partial, out.n_arms * lib.nE, cnt, lib, out, smem);
 }
 
 // Per-patient refit (LSQIntialMask per patient, pkpd_simulation.py:791-800):
@@ -4386,6 +4630,72 @@ int32_t run_segment_discovery(const double* x, int64_t ldx, const int8_t* arm, i
                           iters_out, stream);
 }
 
+// irregular-grid Gram (+ fused finalize / STLSQ when sp.enabled): insite_gram_irregular_f64 /
+// insite_sindy_fit_irregular_f64.  One 64-patient tile per wave, strided over the grid (seg_grid).
+template <int W, int VEC, int NARM>
+void launch_gram_irr(bool fuse7, hipStream_t st, const double* x, int64_t ldx, const double* t_obs, int64_t ld_t,
+                     const int32_t* n_obs, const double* u, const int8_t* arm, int64_t N, int T_max, const LibDesc& lib,
+                     double* part, unsigned* cnt, const GramOut& out) {
+  const dim3 grid((unsigned)seg_grid(N));
+  if (fuse7)
+    gram_irr_kernel<W, VEC, NARM, 7><<<grid, kBlock, 0, st>>>(x, ldx, t_obs, ld_t, n_obs, u, arm, N, T_max, lib, part,
+                                                              cnt, out);
+  else
+    gram_irr_kernel<W, VEC, NARM, 0><<<grid, kBlock, 0, st>>>(x, ldx, t_obs, ld_t, n_obs, u, arm, N, T_max, lib, part,
+                                                              cnt, out);
+}
+
+int32_t run_irregular_discovery(const double* x, int64_t ldx, const double* t_obs, int64_t ld_t, const int32_t* n_obs,
+                                const double* u, const int8_t* arm, int64_t n_patients, int32_t T_max,
+                                int32_t n_statics, int32_t n_arms, const int8_t* exps, int32_t n_terms, int32_t fd_kind,
+                                double* G_out, double* b_out, double* mom_out, void* workspace, size_t workspace_bytes,
+                                void* stream, const StlsqParams& sp, double* coef_out, int8_t* mask_out,
+                                int32_t* iters_out) {
+  if (n_patients < 0 || T_max < 0 || !G_out || !b_out || n_arms < 1 || n_arms > INSITE_MAX_ARMS || ldx < T_max ||
+      ld_t < T_max || n_statics < 0 || n_terms < 0)
+    return INSITE_E_INVALID_ARG;
+  if (fd_kind != INSITE_FD_NONUNIFORM2 && fd_kind != INSITE_FD_NONUNIFORM4) return INSITE_E_INVALID_ARG;
+  if (n_patients > 0 && (!x || !t_obs || !n_obs || !arm || (n_statics > 0 && !u))) return INSITE_E_INVALID_ARG;
+  LibDesc lib;
+  int32_t st = build_lib(exps, n_terms, n_statics, &lib);
+  if (st != INSITE_OK) return st;
+  if (!workspace || workspace_bytes < insite_gram_irregular_workspace_bytes(n_patients, n_arms, n_terms))
+    return INSITE_E_WORKSPACE;
+  if (n_patients == 0) return INSITE_OK;
+  lib.mfma = 0;
+  hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
+  const int na = narm_pad(n_arms);
+  unsigned* cnt = static_cast<unsigned*>(workspace);
+  double* part = reinterpret_cast<double*>(static_cast<char*>(workspace) + kGramWsHeader);
+  if (n_statics == 0) u = x;  // loaded unconditionally (values unused when U = 0)
+  // 16-B loads when every row segment of both arrays is 16-B aligned and a pair never crosses T_max
+  const bool vec2 = ldx % 2 == 0 && ld_t % 2 == 0 && T_max % 2 == 0 &&
+                    ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(t_obs)) & 15u) == 0;
+  const bool fuse = sp.enabled && n_terms == 7;  // the degree-2 interaction library of C5: STLSQ in the tail
+  const GramOut go{G_out, b_out, n_arms, coef_out, mask_out, iters_out, sp, mom_out};
+#define INSITE_IRR_LAUNCH(WW, VV, NA) \
+  launch_gram_irr<WW, VV, NA>(fuse, hs, x, ldx, t_obs, ld_t, n_obs, u, arm, n_patients, T_max, lib, part, cnt, go)
+#define INSITE_IRR_ARMS(WW, VV)                 \
+  do {                                          \
+    if (na == 1) INSITE_IRR_LAUNCH(WW, VV, 1);  \
+    else if (na == 2) INSITE_IRR_LAUNCH(WW, VV, 2); \
+    else INSITE_IRR_LAUNCH(WW, VV, 4);          \
+  } while (0)
+  if (fd_kind == INSITE_FD_NONUNIFORM2) {
+    if (vec2) INSITE_IRR_ARMS(3, 2);
+    else INSITE_IRR_ARMS(3, 1);
+  } else {
+    if (vec2) INSITE_IRR_ARMS(5, 2);
+    else INSITE_IRR_ARMS(5, 1);
+  }
+#undef INSITE_IRR_ARMS
+#undef INSITE_IRR_LAUNCH
+  st = launch_status();
+  if (st != INSITE_OK || !sp.enabled || fuse) return st;
+  return insite_stlsq_f64(G_out, b_out, n_arms, n_terms, sp.thr, sp.alpha, sp.max_iter, sp.unbias, coef_out, mask_out,
+                          iters_out, stream);
+}
+
 template <int METHOD, int NARM, bool PERROW>
 void launch_rollout_a(int av, bool yv2, dim3 grid, hipStream_t st, const RolloutArgs& ra, const LibDesc& lib) {
   if (yv2) {
@@ -5179,6 +5489,42 @@ int32_t insite_masked_sse_f64(const double* pred, int64_t ld_pred, double scale,
   sse_finalize<<<dim3((W + kBlock - 1) / kBlock), kBlock, 0, hs>>>(part, grid, T, per_step_out,
                                                                     per_step_cnt_out, last_out);
   return launch_status();
+}
+
+// ---- discovery on irregular observation grids (insite_irregular.h) ----
+int32_t insite_irregular_abi_version(void) { return INSITE_IRREGULAR_ABI_VERSION; }
+
+size_t insite_gram_irregular_workspace_bytes(int64_t n_patients, int32_t n_arms, int32_t n_terms) {
+  (void)n_terms;
+  if (n_patients < 0 || n_arms < 1 || n_arms > INSITE_MAX_ARMS) return 0;
+  // block partials [grid][n_arms * nE] and <= kTailMaxGroups group partials (gram_tail), nE <= 54
+  const size_t ent = (size_t)n_arms * (INSITE_MAX_TERMS * (INSITE_MAX_TERMS + 1) / 2 + INSITE_MAX_TERMS);
+  return kGramWsHeader + ((size_t)seg_grid(n_patients) + kTailMaxGroups) * ent * sizeof(double);
+}
+
+int32_t insite_gram_irregular_f64(const double* x, int64_t ldx, const double* t_obs, int64_t ld_t,
+                                  const int32_t* n_obs, const double* u, const int8_t* arm, int64_t n_patients,
+                                  int32_t T_max, int32_t n_statics, int32_t n_arms, const int8_t* exps,
+                                  int32_t n_terms, int32_t fd_kind, double* G_out, double* b_out, double* mom_out,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  StlsqParams sp{0.0, 0.0, 0, 0, 0};
+  return run_irregular_discovery(x, ldx, t_obs, ld_t, n_obs, u, arm, n_patients, T_max, n_statics, n_arms, exps,
+                                 n_terms, fd_kind, G_out, b_out, mom_out, workspace, workspace_bytes, stream, sp,
+                                 nullptr, nullptr, nullptr);
+}
+
+int32_t insite_sindy_fit_irregular_f64(const double* x, int64_t ldx, const double* t_obs, int64_t ld_t,
+                                       const int32_t* n_obs, const double* u, const int8_t* arm, int64_t n_patients,
+                                       int32_t T_max, int32_t n_statics, int32_t n_arms, const int8_t* exps,
+                                       int32_t n_terms, int32_t fd_kind, double threshold, double alpha,
+                                       int32_t max_iter, int32_t unbias, double* G_out, double* b_out,
+                                       double* coef_out, int8_t* mask_out, int32_t* iters_out, double* mom_out,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+  if (!coef_out || max_iter < 0 || !(threshold >= 0.0) || !(alpha >= 0.0)) return INSITE_E_INVALID_ARG;
+  StlsqParams sp{threshold, alpha, max_iter, unbias, 1};
+  return run_irregular_discovery(x, ldx, t_obs, ld_t, n_obs, u, arm, n_patients, T_max, n_statics, n_arms, exps,
+                                 n_terms, fd_kind, G_out, b_out, mom_out, workspace, workspace_bytes, stream, sp,
+                                 coef_out, mask_out, iters_out);
 }
 
 }  // extern "C"

@@ -26,6 +26,8 @@ ABI_VERSION = 9
 INSITE_OK = 0
 INSITE_E_UNSUPPORTED = -2   # include/insite_hip.h
 FD_SMOOTHED4, FD_ORDER4, FD_ORDER1, FD_SMOOTHED1 = 0, 1, 2, 3
+FD_NONUNIFORM2, FD_NONUNIFORM4 = 4, 5   # include/insite_irregular.h
+IRREGULAR_ABI_VERSION = 1
 METHOD_EULER, METHOD_RK4 = 0, 1
 LAYOUT_PATIENT_MAJOR, LAYOUT_TIME_MAJOR, LAYOUT_TIME_MAJOR_BITS, LAYOUT_PATIENT_MAJOR_BITS = 0, 1, 2, 3
 MAX_TERMS, MAX_STATICS, MAX_ARMS, MAX_STATE_DEGREE = 9, 3, 4, 1
@@ -75,6 +77,14 @@ EXPORTS = (
     "insite_rollout_poly_f64",
     "insite_threefry2x32_iota_u32",
     "insite_refit_rollout_moments_f64",
+)
+
+# the extension header include/insite_irregular.h (same shared library, its own ABI version)
+EXT_EXPORTS = (
+    "insite_irregular_abi_version",
+    "insite_gram_irregular_workspace_bytes",
+    "insite_gram_irregular_f64",
+    "insite_sindy_fit_irregular_f64",
 )
 
 
@@ -184,6 +194,14 @@ _SIGNATURES = {
                                          _vp]),
     "insite_rollout_poly_f64": (_c_i32, [_vp, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _c_i32, _c_i64, _c_i32, _c_i32,
                                          _c_i32, _c_f64, _c_i32, _c_i32, _c_f64, _vp, _c_i64, _c_i32, _vp]),
+    # insite_irregular.h
+    "insite_irregular_abi_version": (_c_i32, []),
+    "insite_gram_irregular_workspace_bytes": (_c_size, [_c_i64, _c_i32, _c_i32]),
+    "insite_gram_irregular_f64": (_c_i32, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i32, _c_i32, _c_i32,
+                                           _vp, _c_i32, _c_i32, _vp, _vp, _vp, _vp, _c_size, _vp]),
+    "insite_sindy_fit_irregular_f64": (_c_i32, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i32, _c_i32,
+                                                _c_i32, _vp, _c_i32, _c_i32, _c_f64, _c_f64, _c_i32, _c_i32, _vp, _vp,
+                                                _vp, _vp, _vp, _vp, _vp, _c_size, _vp]),
 }
 
 
@@ -210,6 +228,9 @@ def load(path: str | None = None):
         v = lib.insite_abi_version()
         if v != ABI_VERSION:
             raise InsiteLibraryError(f"ABI version mismatch: library {v}, bindings {ABI_VERSION}")
+        v = lib.insite_irregular_abi_version()
+        if v != IRREGULAR_ABI_VERSION:
+            raise InsiteLibraryError(f"irregular ABI version mismatch: library {v}, bindings {IRREGULAR_ABI_VERSION}")
         if path is None:
             _lib = lib
         return lib

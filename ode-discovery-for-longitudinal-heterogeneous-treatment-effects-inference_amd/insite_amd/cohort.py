@@ -156,6 +156,55 @@ def irregular_grid(n_patients: int, seed: int, device, t_max: float = MAX_TIME_H
 
 
 @dataclass
+class IrregularCohort:
+    x: torch.Tensor          # [N, T_max] f64 patient-major samples at the patient's own times (zeros past the grid)
+    t_obs: torch.Tensor      # [N, T_max] f64 patient-major observation times (zeros past the grid)
+    n_obs: torch.Tensor      # [N] int32 samples per patient
+    u: torch.Tensor          # [N, 2] f64 statics (c_0, c_1)
+    arm: torch.Tensor        # [N] int8 factual arm
+    C: torch.Tensor          # [N, 2] f64 hidden rates
+    T_max: int
+    lib: PolyLibrary
+
+
+def irregular_cohort(n_patients: int, seed: int, device, equation: str = "EQ_4_C", noise: float | None = None,
+                     conf_coeff: float = 2.0, t_max: float = MAX_TIME_HORIZON, n_min: int = 20,
+                     n_max: int = 60) -> IrregularCohort:
+    """C5 cohort for discovery on irregular grids: ``irregular_grid`` times and the true decay model evaluated
+    at them in closed form, x_p(t) = y0_p exp(-C_a t) with ``synthetic_pkpd``'s distributions (arm a = the
+    patient's factual arm), plus ``noise`` * N(0, 1) (default: 0.01 for EQ_4_B/C/D, none for EQ_4_A).  Arrays are
+    patient-major with zeros past each patient's grid (``ops.sindy_fit_irregular``'s layout)."""
+    dev = torch.device(device)
+    g = _gen(seed, dev)
+    N = int(n_patients)
+    f64 = torch.float64
+    c = torch.randn((N, 2), generator=g, device=dev, dtype=f64) * 0.05 + 0.5
+    C = c.clone()
+    if equation in ("EQ_4_C", "EQ_4_D"):
+        C[:, 0] += 0.05
+        C[:, 1] += 0.15
+        if equation == "EQ_4_D":
+            C += torch.randn((1, 2), generator=g, device=dev, dtype=f64) * 0.25
+    elif equation not in ("EQ_4_A", "EQ_4_B"):
+        raise NotImplementedError(equation)
+    y0 = torch.rand((N,), generator=g, device=dev, dtype=f64) * (MAX_VALUE - 1.0) + 1.0
+    prob = torch.sigmoid((conf_coeff / MAX_VALUE) * (y0 - MAX_VALUE / 2.0))
+    arm = (torch.rand((N,), generator=g, device=dev, dtype=f64) < prob).to(torch.int8)
+    t_tm, n_obs = irregular_grid(N, seed + 104729, dev, t_max=t_max, n_min=n_min, n_max=n_max)
+    own = torch.arange(n_max, device=dev)[None, :] < n_obs[:, None]
+    t_obs = torch.where(own, t_tm.t(), torch.zeros((), dtype=f64, device=dev)).contiguous()
+    rate = torch.where(arm.bool(), C[:, 1], C[:, 0])
+    x = y0[:, None] * torch.exp(-rate[:, None] * t_obs)
+    if noise is None:
+        noise = OBSERVATION_NOISE if equation.split("_")[-1] in ("B", "C", "D") else 0.0
+    if noise:
+        x = x + float(noise) * torch.randn((N, n_max), generator=g, device=dev, dtype=f64)
+    x = torch.where(own, x, torch.zeros((), dtype=f64, device=dev)).contiguous()
+    return IrregularCohort(x=x, t_obs=t_obs, n_obs=n_obs, u=c.contiguous(), arm=arm, C=C, T_max=n_max,
+                           lib=polynomial_library(2, 2, True))
+
+
+@dataclass
 class SegmentCohort:
     x: torch.Tensor          # [T + 1, N] f64 time-major samples (x[0] = y0)
     u: torch.Tensor          # [N, U] f64 statics

@@ -551,6 +551,114 @@ def plan_sindy_fit_segments(x, arm, seq_len, u, dt, lib, threshold, alpha, max_i
     return Plan(name, args, dev, out, keep)
 
 
+IRREGULAR_FD_KINDS = {"nonuniform2": _lib.FD_NONUNIFORM2, "nonuniform4": _lib.FD_NONUNIFORM4}
+
+
+def check_irregular_grid(t_obs: torch.Tensor, n_obs: torch.Tensor) -> None:
+    """Raise ``ValueError`` unless every patient's first ``n_obs`` times are finite and strictly increasing
+    (pysindy raises on such a grid; the C entry points leave the check to the caller).  Runs on the device and
+    synchronises once; what lies past ``n_obs`` is not looked at."""
+    T = t_obs.size(1)
+    k = torch.arange(T, device=t_obs.device)
+    own = k[None, :] < n_obs[:, None].clamp(max=T)
+    bad = own & ~torch.isfinite(t_obs)
+    bad[:, 1:] |= own[:, 1:] & ~(t_obs[:, 1:] > t_obs[:, :-1])
+    if bool(bad.any()):
+        p = int(bad.any(dim=1).nonzero()[0])
+        raise ValueError(f"t_obs: the grid of patient {p} is not finite and strictly increasing within n_obs")
+
+
+def _prep_irregular(x, t_obs, n_obs, u, arm, lib, n_arms, fd, workspace, out, moments, validate, stlsq_args=None):
+    """Validate the irregular-grid discovery inputs and pack the C arguments (insite_irregular.h)."""
+    if fd not in IRREGULAR_FD_KINDS:
+        raise ValueError(f"fd must be one of {sorted(IRREGULAR_FD_KINDS)}")
+    _dev("x", x, torch.float64, 2)
+    _dev("t_obs", t_obs, torch.float64, 2)
+    _dev("n_obs", n_obs, torch.int32, 1)
+    _dev("arm", arm, torch.int8, 1)
+    if not 1 <= n_arms <= _lib.MAX_ARMS:
+        raise ValueError(f"n_arms must be in [1, {_lib.MAX_ARMS}]")
+    N, T_max = x.shape
+    if tuple(t_obs.shape) != (N, T_max) or n_obs.numel() != N or arm.numel() != N:
+        raise ValueError("x and t_obs must be [N, T_max], n_obs and arm [N]")
+    if lib.n_statics:
+        _dev("u", u, torch.float64, 2)
+        if u.size(0) != N or u.size(1) != lib.n_statics or u.stride(0) != lib.n_statics:
+            raise ValueError("u must be a contiguous [N, n_statics] tensor")
+    if validate:
+        check_irregular_grid(t_obs, n_obs)
+    L = _lib.load()
+    F = lib.n_terms
+    dev = x.device
+    ws = _ws(workspace, dev, "disc").get(L.insite_gram_irregular_workspace_bytes(N, n_arms, F), dev)
+    tab = lib.ctypes_table()
+    # a one-row tensor may carry any row stride: pass one the ABI accepts
+    head = (_p(x), max(x.stride(0), T_max), _p(t_obs), max(t_obs.stride(0), T_max), _p(n_obs),
+            _p(u) if lib.n_statics else ctypes.c_void_p(0), _p(arm), N, T_max, lib.n_statics, n_arms,
+            tab.ctypes.data_as(ctypes.c_void_p), F, IRREGULAR_FD_KINDS[fd])
+    n_fix = 2 if stlsq_args is None else 5
+    if out is None:
+        out = (torch.zeros((n_arms, F, F), dtype=torch.float64, device=dev),
+               torch.zeros((n_arms, F), dtype=torch.float64, device=dev))
+        if stlsq_args is not None:
+            out = (torch.zeros((n_arms, F), dtype=torch.float64, device=dev),
+                   torch.zeros((n_arms, F), dtype=torch.int8, device=dev),
+                   torch.zeros((n_arms,), dtype=torch.int32, device=dev)) + out
+        if moments:
+            out = out + (torch.zeros((N, 5), dtype=torch.float64, device=dev),)
+    if len(out) != n_fix + (1 if moments else 0):
+        raise ValueError(f"out must hold {n_fix + (1 if moments else 0)} tensors")
+    mom = out[n_fix] if moments else None
+    keep = (x, t_obs, n_obs, u, arm, tab, ws, *out)
+    if stlsq_args is None:
+        G, b = out[:2]
+        return "insite_gram_irregular_f64", head + (_p(G), _p(b), _p(mom), _p(ws), ws.numel()), dev, out, keep
+    threshold, alpha, max_iter, unbias = stlsq_args
+    coef, mask, iters, G, b = out[:5]
+    args = head + (float(threshold), float(alpha), int(max_iter), int(bool(unbias)), _p(G), _p(b), _p(coef), _p(mask),
+                   _p(iters), _p(mom), _p(ws), ws.numel())
+    return "insite_sindy_fit_irregular_f64", args, dev, out, keep
+
+
+def gram_irregular(x: torch.Tensor, t_obs: torch.Tensor, n_obs: torch.Tensor, u: torch.Tensor, arm: torch.Tensor,
+                   lib: PolyLibrary, n_arms: int = 2, fd: str = "nonuniform4", workspace: Workspace | None = None,
+                   out: tuple | None = None, moments: bool = False, validate: bool = False):
+    """Per-arm Gram of the discovery regression on per-patient irregular grids (insite_gram_irregular_f64):
+    x, t_obs [N, T_max] patient-major, n_obs [N] int32 samples per patient, arm [N] int8.  ``fd``: "nonuniform2"
+    (three-sample Lagrange derivative = numpy.gradient(x, t, edge_order=2)) or "nonuniform4" (five samples).
+    What lies past ``n_obs`` is never used.  ``validate=True`` checks the grids on the device first (one
+    synchronisation).  Returns (G[A,F,F], b[A,F]) and, with ``moments=True``, the per-patient moments [N, 5]."""
+    return _run(_prep_irregular(x, t_obs, n_obs, u, arm, lib, n_arms, fd, workspace, out, moments, validate))
+
+
+def sindy_fit_irregular(x: torch.Tensor, t_obs: torch.Tensor, n_obs: torch.Tensor, u: torch.Tensor,
+                        arm: torch.Tensor, lib: PolyLibrary, threshold: float, alpha: float, max_iter: int = 100,
+                        unbias: bool = True, n_arms: int = 2, fd: str = "nonuniform4",
+                        workspace: Workspace | None = None, out: tuple | None = None, moments: bool = False,
+                        validate: bool = False):
+    """Discovery on irregular grids (insite_sindy_fit_irregular_f64): the Gram pass of ``gram_irregular`` with the
+    per-arm STLSQ in its finalisation.  Returns (coef[A,F], mask[A,F], iters[A], G[A,F,F], b[A,F]) and, with
+    ``moments=True``, the per-patient moments [N, 5]."""
+    return _run(_prep_irregular(x, t_obs, n_obs, u, arm, lib, n_arms, fd, workspace, out, moments, validate,
+                                (threshold, alpha, max_iter, unbias)))
+
+
+def plan_gram_irregular(x, t_obs, n_obs, u, arm, lib, n_arms=2, fd="nonuniform4", workspace=None, out=None,
+                        moments=False, validate=False) -> Plan:
+    """``gram_irregular`` as a prepared launch; ``plan.out`` = (G, b[, mom])."""
+    name, args, dev, out, keep = _prep_irregular(x, t_obs, n_obs, u, arm, lib, n_arms, fd, _plan_ws(workspace), out,
+                                                 moments, validate)
+    return Plan(name, args, dev, out, keep)
+
+
+def plan_sindy_fit_irregular(x, t_obs, n_obs, u, arm, lib, threshold, alpha, max_iter=100, unbias=True, n_arms=2,
+                             fd="nonuniform4", workspace=None, out=None, moments=False, validate=False) -> Plan:
+    """``sindy_fit_irregular`` as a prepared launch; ``plan.out`` = (coef, mask, iters, G, b[, mom])."""
+    name, args, dev, out, keep = _prep_irregular(x, t_obs, n_obs, u, arm, lib, n_arms, fd, _plan_ws(workspace), out,
+                                                 moments, validate, (threshold, alpha, max_iter, unbias))
+    return Plan(name, args, dev, out, keep)
+
+
 GEN_FD_KINDS = {"smoothed4": _lib.FD_SMOOTHED4, "order4": _lib.FD_ORDER4, "order1": _lib.FD_ORDER1,
                 "smoothed1": _lib.FD_SMOOTHED1}
 

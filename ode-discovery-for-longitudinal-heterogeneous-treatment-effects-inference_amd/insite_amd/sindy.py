@@ -346,6 +346,31 @@ class SINDY:
         logger.info("[Model]: %s", self.global_equation_string)
         return self
 
+    # ------------------------------------------------------------------ irregular observation grids (C5)
+    def fit_irregular(self, x, t_obs, n_obs, u, arm, fd="nonuniform4", validate=True):
+        """Global discovery per arm from trajectories sampled at each patient's own times
+        (insite_sindy_fit_irregular_f64): device tensors x, t_obs [N, T_max] patient-major, n_obs [N] int32,
+        u [N, U], arm [N] int8 (one factual arm per patient).  ``fd``: "nonuniform2" or "nonuniform4" (the
+        Lagrange derivative through 3 / 5 samples; pysindy FiniteDifference(order=2, is_uniform=False) and its
+        five-point form).  Sets ``joint_coefs``, ``global_equation_string`` and the rollout model as ``fit``."""
+        if self.joint_model or self.segment_mode or self.library.state_degree > 1:
+            raise NotImplementedError("fit_irregular covers the per-arm EQ_4 model over the affine library")
+        coef, mask, iters, G, _ = ops.sindy_fit_irregular(x, t_obs, n_obs, u, arm, self.library, self.sindy_threshold,
+                                                          self.sindy_alpha, max_iter=100, unbias=True,
+                                                          n_arms=self.dim_treatments, fd=fd, validate=validate)
+        empty = np.nonzero(G[:, 0, 0].cpu().numpy() == 0)[0]
+        if empty.size:
+            raise ValueError(f"treatment arm(s) {empty.tolist()} have no trajectory long enough for {fd} "
+                             "(pysindy cannot fit an empty trajectory list)")
+        return self._finish_fit(coef, mask, iters)
+
+    def predict_irregular(self, y0, u, arm_bits, t_obs, n_obs, **kwargs):
+        """Adaptive RK45 rollout of the fitted model on per-patient grids: ``ops.rollout_rk45`` with the fitted
+        coefficients (its arguments and layouts; returns (y, step attempts))."""
+        if self._coef_dev is None:
+            raise RuntimeError("fit() first")
+        return ops.rollout_rk45(y0, u, arm_bits, t_obs, n_obs, self._coef_dev, self._roll_library, **kwargs)
+
     # ------------------------------------------------------------------ rollout (A8)
     def _predict_device(self, dataset, tau=1):
         """Standardised open-loop predictions [N, T-1] on the device (sindy.py:371-431); with
