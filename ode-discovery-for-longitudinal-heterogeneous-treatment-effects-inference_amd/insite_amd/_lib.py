@@ -28,6 +28,8 @@ INSITE_E_UNSUPPORTED = -2   # include/insite_hip.h
 FD_SMOOTHED4, FD_ORDER4, FD_ORDER1, FD_SMOOTHED1 = 0, 1, 2, 3
 FD_NONUNIFORM2, FD_NONUNIFORM4 = 4, 5   # include/insite_irregular.h
 IRREGULAR_ABI_VERSION = 1
+WEAK_ABI_VERSION, WEAK_MAX_K = 1, 1024     # include/insite_weak.h
+OPT_SR3, OPT_STLSQ = 0, 1
 METHOD_EULER, METHOD_RK4 = 0, 1
 LAYOUT_PATIENT_MAJOR, LAYOUT_TIME_MAJOR, LAYOUT_TIME_MAJOR_BITS, LAYOUT_PATIENT_MAJOR_BITS = 0, 1, 2, 3
 MAX_TERMS, MAX_STATICS, MAX_ARMS, MAX_STATE_DEGREE = 9, 3, 4, 1
@@ -85,6 +87,16 @@ EXT_EXPORTS = (
     "insite_gram_irregular_workspace_bytes",
     "insite_gram_irregular_f64",
     "insite_sindy_fit_irregular_f64",
+)
+
+# the extension header include/insite_weak.h (same shared library, its own ABI version; a list of its own:
+# EXT_EXPORTS is pinned to insite_irregular.h's functions by tests/test_irregular_oracle.py)
+WEAK_EXPORTS = (
+    "insite_weak_abi_version",
+    "insite_gram_weak_workspace_bytes",
+    "insite_gram_weak_f64",
+    "insite_sr3_f64",
+    "insite_sindy_fit_weak_f64",
 )
 
 
@@ -202,6 +214,16 @@ _SIGNATURES = {
     "insite_sindy_fit_irregular_f64": (_c_i32, [_vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i32, _c_i32,
                                                 _c_i32, _vp, _c_i32, _c_i32, _c_f64, _c_f64, _c_i32, _c_i32, _vp, _vp,
                                                 _vp, _vp, _vp, _vp, _vp, _c_size, _vp]),
+    # insite_weak.h
+    "insite_weak_abi_version": (_c_i32, []),
+    "insite_gram_weak_workspace_bytes": (_c_size, [_c_i64, _c_i32, _c_i32, _c_i32]),
+    "insite_gram_weak_f64": (_c_i32, [_vp, _c_i64, _c_i32, _c_i32, _vp, _vp, _c_i64, _c_i32, _vp, _vp, _vp, _c_i64,
+                                      _c_i32, _c_i32, _vp, _c_i32, _vp, _vp, _vp, _vp, _c_size, _vp]),
+    "insite_sr3_f64": (_c_i32, [_vp, _vp, _c_i64, _c_i32, _c_f64, _c_f64, _c_f64, _c_i32, _c_i32, _vp, _vp, _vp,
+                                _vp]),
+    "insite_sindy_fit_weak_f64": (_c_i32, [_vp, _c_i64, _c_i32, _c_i32, _vp, _vp, _c_i64, _c_i32, _vp, _vp, _vp,
+                                           _c_i64, _c_i32, _c_i32, _vp, _c_i32, _c_i32, _c_f64, _c_f64, _c_f64,
+                                           _c_f64, _c_i32, _c_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_size, _vp]),
 }
 
 
@@ -231,6 +253,9 @@ def load(path: str | None = None):
         v = lib.insite_irregular_abi_version()
         if v != IRREGULAR_ABI_VERSION:
             raise InsiteLibraryError(f"irregular ABI version mismatch: library {v}, bindings {IRREGULAR_ABI_VERSION}")
+        v = lib.insite_weak_abi_version()
+        if v != WEAK_ABI_VERSION:
+            raise InsiteLibraryError(f"weak ABI version mismatch: library {v}, bindings {WEAK_ABI_VERSION}")
         if path is None:
             _lib = lib
         return lib

@@ -659,6 +659,124 @@ def plan_sindy_fit_irregular(x, t_obs, n_obs, u, arm, lib, threshold, alpha, max
     return Plan(name, args, dev, out, keep)
 
 
+WEAK_OPTIMIZERS = {"sr3": _lib.OPT_SR3, "stlsq": _lib.OPT_STLSQ}
+
+
+def _prep_weak(x, W, D, u, arm, rows, lib, n_arms, workspace, out, layout, moments, fit_args=None):
+    """Validate the weak-form discovery inputs and pack the C arguments (insite_weak.h)."""
+    L = _lib.load()
+    N, n_steps, lay = _discovery_inputs(x, u, arm, rows, lib, layout)
+    _dev("W", W, torch.float64, 2)
+    _dev("D", D, torch.float64, 2)
+    K = W.size(0)
+    if tuple(D.shape) != tuple(W.shape) or W.size(1) != n_steps or K < 1:
+        raise ValueError("W and D must both be [K, n_steps]")
+    ldw = max(W.stride(0), n_steps)   # a one-row tensor may carry any row stride
+    if K > 1 and D.stride(0) != W.stride(0):
+        raise ValueError("W and D must share their row stride")
+    if not 1 <= n_arms <= _lib.MAX_ARMS:
+        raise ValueError(f"n_arms must be in [1, {_lib.MAX_ARMS}]")
+    F = lib.n_terms
+    dev = x.device
+    ws = _ws(workspace, dev, "disc").get(L.insite_gram_weak_workspace_bytes(N, n_arms, F, K), dev)
+    tab = lib.ctypes_table()
+    ldx = max(x.stride(0), x.size(1))
+    head = (_p(x), ldx, lay, n_steps, _p(W), _p(D), ldw, K, _p(u) if lib.n_statics else ctypes.c_void_p(0), _p(arm),
+            _p(rows), N, lib.n_statics, n_arms, tab.ctypes.data_as(ctypes.c_void_p), F)
+    n_fix = 2 if fit_args is None else 5
+    if out is None:
+        out = (torch.zeros((n_arms, F, F), dtype=torch.float64, device=dev),
+               torch.zeros((n_arms, F), dtype=torch.float64, device=dev))
+        if fit_args is not None:
+            out = (torch.zeros((n_arms, F), dtype=torch.float64, device=dev),
+                   torch.zeros((n_arms, F), dtype=torch.int8, device=dev),
+                   torch.zeros((n_arms,), dtype=torch.int32, device=dev)) + out
+        if moments:
+            out = out + (torch.zeros((N, 5), dtype=torch.float64, device=dev),)
+    if len(out) != n_fix + (1 if moments else 0):
+        raise ValueError(f"out must hold {n_fix + (1 if moments else 0)} tensors")
+    mom = out[n_fix] if moments else None
+    keep = (x, W, D, u, arm, rows, tab, ws, *out)
+    if fit_args is None:
+        G, b = out[:2]
+        return "insite_gram_weak_f64", head + (_p(G), _p(b), _p(mom), _p(ws), ws.numel()), dev, out, keep
+    optimizer, threshold, alpha, nu, tol, max_iter, unbias = fit_args
+    if optimizer not in WEAK_OPTIMIZERS:
+        raise ValueError(f"optimizer must be one of {sorted(WEAK_OPTIMIZERS)}")
+    coef, mask, iters, G, b = out[:5]
+    args = head + (WEAK_OPTIMIZERS[optimizer], float(threshold), float(alpha), float(nu), float(tol), int(max_iter),
+                   int(bool(unbias)), _p(G), _p(b), _p(coef), _p(mask), _p(iters), _p(mom), _p(ws), ws.numel())
+    return "insite_sindy_fit_weak_f64", args, dev, out, keep
+
+
+def gram_weak(x: torch.Tensor, W: torch.Tensor, D: torch.Tensor, u: torch.Tensor, arm: torch.Tensor,
+              rows: torch.Tensor, lib: PolyLibrary, n_arms: int = 2, workspace: Workspace | None = None,
+              out: tuple | None = None, layout: str = "patient", moments: bool = False):
+    """Per-arm Gram of the weak-form regression (insite_gram_weak_f64): x as ``gram``, W / D [K, n_steps] the
+    quadrature weights of the K test functions and of their derivatives (``weak.test_function_weights``).  A
+    patient with rows < n_steps contributes nothing.  Returns (G[A,F,F], b[A,F]) and, with ``moments=True``, the
+    per-patient moments [N, 5] = {sum c^2, sum c a, sum a^2, sum c d, sum a d}."""
+    return _run(_prep_weak(x, W, D, u, arm, rows, lib, n_arms, workspace, out, layout, moments))
+
+
+def sindy_fit_weak(x: torch.Tensor, W: torch.Tensor, D: torch.Tensor, u: torch.Tensor, arm: torch.Tensor,
+                   rows: torch.Tensor, lib: PolyLibrary, threshold: float, optimizer: str = "sr3", alpha: float = 0.5,
+                   nu: float = 1.0, tol: float = 1e-1, max_iter: int = 1000, unbias: bool = True, n_arms: int = 2,
+                   workspace: Workspace | None = None, out: tuple | None = None, layout: str = "patient",
+                   moments: bool = False):
+    """Weak-form discovery (insite_sindy_fit_weak_f64): the Gram pass of ``gram_weak`` followed on the stream by
+    the per-arm solve, ``optimizer`` "sr3" (``sr3``: threshold, nu, tol) or "stlsq" (``stlsq``: threshold, alpha).
+    Returns (coef[A,F], mask[A,F], iters[A], G[A,F,F], b[A,F]) and, with ``moments=True``, the moments [N, 5]."""
+    return _run(_prep_weak(x, W, D, u, arm, rows, lib, n_arms, workspace, out, layout, moments,
+                           (optimizer, threshold, alpha, nu, tol, max_iter, unbias)))
+
+
+def plan_gram_weak(x, W, D, u, arm, rows, lib, n_arms=2, workspace=None, out=None, layout="patient",
+                   moments=False) -> Plan:
+    """``gram_weak`` as a prepared launch; ``plan.out`` = (G, b[, mom])."""
+    name, args, dev, out, keep = _prep_weak(x, W, D, u, arm, rows, lib, n_arms, _plan_ws(workspace), out, layout,
+                                            moments)
+    return Plan(name, args, dev, out, keep)
+
+
+def plan_sindy_fit_weak(x, W, D, u, arm, rows, lib, threshold, optimizer="sr3", alpha=0.5, nu=1.0, tol=1e-1,
+                        max_iter=1000, unbias=True, n_arms=2, workspace=None, out=None, layout="patient",
+                        moments=False) -> Plan:
+    """``sindy_fit_weak`` as a prepared launch; ``plan.out`` = (coef, mask, iters, G, b[, mom])."""
+    name, args, dev, out, keep = _prep_weak(x, W, D, u, arm, rows, lib, n_arms, _plan_ws(workspace), out, layout,
+                                            moments, (optimizer, threshold, alpha, nu, tol, max_iter, unbias))
+    return Plan(name, args, dev, out, keep)
+
+
+def _prep_sr3(G, b, threshold, nu, tol, max_iter, unbias, out):
+    _dev("G", G, torch.float64)
+    _dev("b", b, torch.float64)
+    F = G.shape[-1]
+    S = G.numel() // (F * F)
+    if b.numel() != S * F or not G.is_contiguous() or not b.is_contiguous():
+        raise ValueError("G/b must be contiguous [S,F,F] / [S,F]")
+    if out is None:
+        out = (torch.empty((S, F), dtype=torch.float64, device=G.device),
+               torch.empty((S, F), dtype=torch.int8, device=G.device),
+               torch.empty((S,), dtype=torch.int32, device=G.device))
+    coef, mask, iters = out
+    args = (_p(G), _p(b), S, F, float(threshold), float(nu), float(tol), int(max_iter), int(bool(unbias)), _p(coef),
+            _p(mask), _p(iters))
+    return "insite_sr3_f64", args, G.device, out, (G, b, *out)
+
+
+def sr3(G: torch.Tensor, b: torch.Tensor, threshold: float, nu: float = 1.0, tol: float = 1e-1, max_iter: int = 1000,
+        unbias: bool = True, out: tuple | None = None):
+    """Batched SR3 (l1 prox, column-normalised) on Gram systems (insite_sr3_f64).  G [S,F,F], b [S,F]; returns
+    (coef[S,F], mask[S,F], iters[S]); a system whose Cholesky fails gets iters = -1 and NaN coefficients."""
+    return _run(_prep_sr3(G, b, threshold, nu, tol, max_iter, unbias, out))
+
+
+def plan_sr3(G, b, threshold, nu=1.0, tol=1e-1, max_iter=1000, unbias=True, out=None) -> Plan:
+    name, args, dev, out, keep = _prep_sr3(G, b, threshold, nu, tol, max_iter, unbias, out)
+    return Plan(name, args, dev, out, keep)
+
+
 GEN_FD_KINDS = {"smoothed4": _lib.FD_SMOOTHED4, "order4": _lib.FD_ORDER4, "order1": _lib.FD_ORDER1,
                 "smoothed1": _lib.FD_SMOOTHED1}
 

@@ -29,7 +29,9 @@ is folded per treatment combination into the per-arm rollout; with ``insite: tru
 GPU (``insite_refine_general_f64``: the joint model's coefficients act on the treatment combinations their
 inputs switch on; the degree-4 library runs the state-polynomial refinement kernels).  The degree-4 library
 on the treatment-segment datasets runs ``insite_gen_gram_segments_f64`` (per-arm power moments of the
-segment rows).  Not on the MI355X path (raises ``NotImplementedError``): weak SINDy.
+segment rows).  Weak SINDy (the reference's ``wsindy`` backbone: WeakPDELibrary(K=100) + SR3) runs through the
+model key ``weak_form`` (``fit_weak``: ``insite_sindy_fit_weak_f64``); the key ``wsindy: true``
+itself still raises ``NotImplementedError``.
 """
 from __future__ import annotations
 
@@ -38,7 +40,7 @@ import logging
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, weak
 from .library import polynomial_library
 
 logger = logging.getLogger(__name__)
@@ -139,6 +141,11 @@ class SINDY:
         self.joint_model = bool(m("joint_model", False))
         self.insite = bool(m("insite", False))
         self.wsindy = bool(m("wsindy", False))
+        self.weak_form = bool(m("weak_form", False))    # the reference's wsindy backbone on the GPU (fit_weak)
+        self.weak_K = int(m("weak_K", weak.DEFAULT_K))
+        self.weak_p = int(m("weak_p", weak.DEFAULT_P))
+        self.weak_seed = m("weak_seed")
+        self.weak_optimizer = str(m("weak_optimizer", "sr3"))
         self.use_smoothed_finite_difference = bool(m("use_smoothed_finite_difference", False))
         self.dataset_name = str(m("dataset_name", ""))
         # cancer_sim / EQ_5: treatment-segment split, FiniteDifference(order=1), one fit per arm of
@@ -171,7 +178,10 @@ class SINDY:
             raise NotImplementedError(f"dataset {self.dataset_name!r}: this build covers the PK/PD EQ_4 family and "
                                       "the treatment-segment datasets (cancer_sim, EQ_5_*)")
         if self.wsindy:
-            raise NotImplementedError("weak SINDy (wsindy: true) is not on the MI355X path")
+            raise NotImplementedError("weak SINDy (wsindy: true) is not on the MI355X path; "
+                                      "the GPU weak form is model.weak_form (+backbone=weak)")
+        if self.weak_optimizer not in ops.WEAK_OPTIMIZERS:
+            raise ValueError(f"weak_optimizer must be one of {sorted(ops.WEAK_OPTIMIZERS)}")
         if self.integrator not in ops.METHODS:
             raise ValueError(f"integrator must be one of {sorted(ops.METHODS)}")
 
@@ -302,6 +312,9 @@ class SINDY:
     def fit(self, train_f, val_f=None):
         """Global discovery per arm (sindy.py:145-336): one Gram pass + STLSQ on the GPU."""
         self.prepare_data()
+        if self.weak_form:
+            return self.fit_weak(train_f, K=self.weak_K, p=self.weak_p, seed=self.weak_seed,
+                                 optimizer=self.weak_optimizer)
         if self.joint_model:
             return self._fit_joint(train_f)
         if self.segment_mode:
@@ -328,7 +341,7 @@ class SINDY:
     def _finish_fit(self, coef, mask, iters):
         iters_h = iters.cpu().numpy()
         if np.any(iters_h < 0):
-            raise np.linalg.LinAlgError("STLSQ ridge system is not positive definite")
+            raise np.linalg.LinAlgError("STLSQ / SR3 system is not positive definite")
         self.joint_coefs = coef.cpu().numpy()
         self.coef_mask = mask.cpu().numpy().astype(bool)
         self.n_iter = iters_h
@@ -345,6 +358,35 @@ class SINDY:
         self._coef_dev = torch.as_tensor(np.ascontiguousarray(rhs), device=self.device)
         logger.info("[Model]: %s", self.global_equation_string)
         return self
+
+    # ------------------------------------------------------------------ weak form (the reference's wsindy backbone)
+    def fit_weak(self, train_f, K=weak.DEFAULT_K, p=weak.DEFAULT_P, H=None, seed=None, optimizer="sr3"):
+        """Weak-form discovery per arm (sindy.py:218-239: WeakPDELibrary(K) + SR3(l1, normalize_columns)) in one
+        Gram pass + per-arm solve on the GPU (insite_sindy_fit_weak_f64).  The grid is the reference's
+        t_train = arange(T) dt with T = the training rows (seq_len - 1); K subdomains with centres
+        ``weak.draw_centres(T, dt, K, seed)``, half-width ``H`` (default L / 20) and exponent ``p``.  ``optimizer``:
+        "sr3" (threshold = sindy_threshold, nu = 1, tol = 1e-1, max_iter = 1000) or "stlsq" (sindy_threshold,
+        sindy_alpha).  Sets what ``fit`` sets."""
+        if self.joint_model or self.segment_mode or self.library.state_degree > 1:
+            raise NotImplementedError("fit_weak covers the per-arm EQ_4 model over the affine library")
+        self.prepare_data()
+        x, u, arm, rows = self.de_format(train_f)
+        T = int(rows.max().item())
+        if T < 2:
+            raise ValueError("the weak form needs trajectories of at least 2 rows")
+        # sorted: the sum over the subdomains does not depend on their order, and the kernel skips the all-zero
+        # tiles of 16 consecutive rows of W | D
+        centres = np.sort(weak.draw_centres(T, self.dt, K, seed, H=H))
+        W, D = weak.test_function_weights(T, self.dt, centres, H=H, p=p, device=self.device)
+        xs = x[:, :T]
+        coef, mask, iters, G, _ = ops.sindy_fit_weak(xs, W, D, u, arm, rows, self.library, self.sindy_threshold,
+                                                     optimizer=optimizer, alpha=self.sindy_alpha,
+                                                     n_arms=self.dim_treatments)
+        empty = np.nonzero(G[:, 0, 0].cpu().numpy() == 0)[0]
+        if empty.size:
+            raise ValueError(f"treatment arm(s) {empty.tolist()} have no trajectory of {T} rows "
+                             "(pysindy cannot fit an empty trajectory list)")
+        return self._finish_fit(coef, mask, iters)
 
     # ------------------------------------------------------------------ irregular observation grids (C5)
     def fit_irregular(self, x, t_obs, n_obs, u, arm, fd="nonuniform4", validate=True):
