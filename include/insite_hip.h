@@ -276,8 +276,16 @@ int32_t insite_sindy_fit_per_patient_f64(const double* x, int64_t ldx, int32_t l
  * per-patient refit needs); insite_fit_per_patient_moments_f64 is the per-patient STLSQ of
  * insite_sindy_fit_per_patient_f64 from those moments (global_coef on the device: the fused fit's
  * coef_out, or the all-reduced model at N > 1).  Together they replace insite_sindy_fit_f64 +
- * insite_sindy_fit_per_patient_f64, which read x twice.  Requires the library to fit the MFMA Gram plan
- * (n_arms * n_terms <= 16; else INSITE_E_UNSUPPORTED).  Workspace: insite_gram_workspace_bytes. */
+ * insite_sindy_fit_per_patient_f64, which read x twice.  Requires the library to fit the MFMA Gram plan, else
+ * INSITE_E_UNSUPPORTED; the plan fits when all three hold:
+ *   - every static exponent of the table is <= 2;
+ *   - the Gram needs at most 16 distinct (atom, moment) columns, an atom being a distinct tuple of static
+ *     exponents among the columns (plus the all-zero tuple, which b needs, when no column has it): entry (i, k),
+ *     i <= k, of G needs (atom of k, sum x^(e_i + e_k)), entry i of b needs (1, sum xdot x^e_i), e = the state
+ *     exponents;
+ *   - P * n_terms <= 16, P = n_arms padded to 1, 2 or 4: three arms count as four, so 3 arms x 5 terms is
+ *     refused although 15 <= 16.
+ * Workspace: insite_gram_workspace_bytes. */
 int32_t insite_gram_moments_f64(const double* x, int64_t ldx, int32_t layout, int32_t n_steps, const double* u,
                                 const int8_t* arm, const int32_t* rows, int64_t n_patients, int32_t n_statics,
                                 int32_t n_arms, const int8_t* exps, int32_t n_terms, int32_t fd_kind, double dt,

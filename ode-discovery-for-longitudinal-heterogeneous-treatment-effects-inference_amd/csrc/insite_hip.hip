@@ -1080,7 +1080,9 @@ __device__ __forceinline__ void gram_body(const int vblk, const int vgrid, doubl
         else small_trajectory<7>(xrow, st, w, Sx, Sxx, Sd, Sdx);
       }
     }
-    if (s0 >= Lmax && !(SMOOTH && first)) continue;  // nothing owned by this work piece (uniform)
+    // nothing owned by this work piece (uniform) -- but a moments pass still writes its patients' (zero) moments:
+    // a wave whose patients all have fewer than 5 rows left mom_out unwritten without smoothing
+    if (s0 >= Lmax && !((SMOOTH || MOM != 0) && first)) continue;
     if constexpr (MOM != 0) {  // 1: moments only (partial = the [N, 5] moments); 2: moments to out.mom + the Gram
       if (p < N) {
         double* mrow = (MOM == 1 ? partial : out.mom) + p * 5;
