@@ -72,6 +72,7 @@ def test_fused_matches_separate_calls(dev, N, T, Nr, Tr, gblocks):
             assert (rows == T - 2).all()
             Gr, br = R.gram_moments_vectorized(x, u, arm, T - 2, disc.dt, exps)
         np.testing.assert_allclose(G.cpu().numpy(), Gr, rtol=1e-10, atol=1e-8)
+        np.testing.assert_allclose(b.cpu().numpy(), br, rtol=1e-10, atol=1e-8)
         cr = np.stack([R.stlsq_gram(Gr[a], br[a], 0.1, 0.5)[0] for a in range(2)])
         assert np.array_equal(mask.cpu().numpy() != 0, cr != 0)
         assert np.max(np.abs(coef.cpu().numpy() - cr)) < 1e-8
@@ -184,6 +185,7 @@ def test_deferred_stream_matches_separate_calls(dev, N, T, Nr, Tr, gblocks):
             Gr, br = R.gram_moments(x, d.u.cpu().numpy(), d.arm.cpu().numpy().astype(np.int64),
                                     d.rows.cpu().numpy(), d.dt, lib.exps.astype(np.int64))
             np.testing.assert_allclose(G.cpu().numpy(), Gr, rtol=1e-10, atol=1e-8)
+            np.testing.assert_allclose(b.cpu().numpy(), br, rtol=1e-10, atol=1e-8)
             cr = np.stack([R.stlsq_gram(Gr[a], br[a], 0.1, 0.5)[0] for a in range(2)])
             assert np.array_equal(mask.cpu().numpy() != 0, cr != 0)
             assert np.max(np.abs(coef.cpu().numpy() - cr)) < 1e-8
