@@ -30,6 +30,7 @@ FD_NONUNIFORM2, FD_NONUNIFORM4 = 4, 5   # include/insite_irregular.h
 IRREGULAR_ABI_VERSION = 1
 WEAK_ABI_VERSION, WEAK_MAX_K = 1, 1024     # include/insite_weak.h
 OPT_SR3, OPT_STLSQ = 0, 1
+BOOTSTRAP_ABI_VERSION, BOOT_MAX_REPLICATES = 1, 16384   # include/insite_bootstrap.h
 METHOD_EULER, METHOD_RK4 = 0, 1
 LAYOUT_PATIENT_MAJOR, LAYOUT_TIME_MAJOR, LAYOUT_TIME_MAJOR_BITS, LAYOUT_PATIENT_MAJOR_BITS = 0, 1, 2, 3
 MAX_TERMS, MAX_STATICS, MAX_ARMS, MAX_STATE_DEGREE = 9, 3, 4, 1
@@ -97,6 +98,15 @@ WEAK_EXPORTS = (
     "insite_gram_weak_f64",
     "insite_sr3_f64",
     "insite_sindy_fit_weak_f64",
+)
+
+# the extension header include/insite_bootstrap.h (same shared library, its own ABI version; a list of its own:
+# EXT_EXPORTS and WEAK_EXPORTS are pinned by tests/test_irregular_oracle.py and tests/test_weak_abi.py)
+BOOT_EXPORTS = (
+    "insite_bootstrap_abi_version",
+    "insite_bootstrap_workspace_bytes",
+    "insite_bootstrap_gram_f64",
+    "insite_sindy_bootstrap_f64",
 )
 
 
@@ -224,6 +234,14 @@ _SIGNATURES = {
     "insite_sindy_fit_weak_f64": (_c_i32, [_vp, _c_i64, _c_i32, _c_i32, _vp, _vp, _c_i64, _c_i32, _vp, _vp, _vp,
                                            _c_i64, _c_i32, _c_i32, _vp, _c_i32, _c_i32, _c_f64, _c_f64, _c_f64,
                                            _c_f64, _c_i32, _c_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_size, _vp]),
+    # insite_bootstrap.h
+    "insite_bootstrap_abi_version": (_c_i32, []),
+    "insite_bootstrap_workspace_bytes": (_c_size, [_c_i64, _c_i32, _c_i32, _c_i32]),
+    "insite_bootstrap_gram_f64": (_c_i32, [_vp, _vp, _vp, _vp, _c_i32, _c_i64, _c_i64, _c_i32, _c_i32, _vp, _c_i32,
+                                           _c_i32, ctypes.c_uint32, _vp, _vp, _vp, _c_size, _vp]),
+    "insite_sindy_bootstrap_f64": (_c_i32, [_vp, _vp, _vp, _vp, _c_i32, _c_i64, _c_i64, _c_i32, _c_i32, _vp, _c_i32,
+                                            _c_i32, ctypes.c_uint32, _c_i32, _c_f64, _c_f64, _c_f64, _c_f64, _c_i32,
+                                            _c_i32, _vp, _vp, _vp, _vp, _vp, _vp, _c_size, _vp]),
 }
 
 
@@ -256,6 +274,9 @@ def load(path: str | None = None):
         v = lib.insite_weak_abi_version()
         if v != WEAK_ABI_VERSION:
             raise InsiteLibraryError(f"weak ABI version mismatch: library {v}, bindings {WEAK_ABI_VERSION}")
+        v = lib.insite_bootstrap_abi_version()
+        if v != BOOTSTRAP_ABI_VERSION:
+            raise InsiteLibraryError(f"bootstrap ABI version mismatch: library {v}, bindings {BOOTSTRAP_ABI_VERSION}")
         if path is None:
             _lib = lib
         return lib

@@ -777,6 +777,113 @@ def plan_sr3(G, b, threshold, nu=1.0, tol=1e-1, max_iter=1000, unbias=True, out=
     return Plan(name, args, dev, out, keep)
 
 
+def _prep_bootstrap(mom, u, arm, rows, lib, n_replicates, seed, n_arms, min_rows, patient_offset, workspace, out,
+                    fit_args=None):
+    """Validate the bootstrap inputs and pack the C arguments (insite_bootstrap.h)."""
+    L = _lib.load()
+    _dev("mom", mom, torch.float64, 2)
+    _dev("arm", arm, torch.int8, 1)
+    N = mom.size(0)
+    if mom.size(1) != 5 or not mom.is_contiguous():
+        raise ValueError("mom must be a contiguous [N, 5] tensor")
+    if rows is not None:
+        _dev("rows", rows, torch.int32, 1)
+    if arm.numel() != N or (rows is not None and rows.numel() != N):
+        raise ValueError("arm/rows must have one entry per patient")
+    if lib.n_statics:
+        _dev("u", u, torch.float64, 2)
+        if u.size(0) != N or u.size(1) != lib.n_statics or u.stride(0) != lib.n_statics:
+            raise ValueError("u must be a contiguous [N, n_statics] tensor")
+    if not 1 <= n_arms <= _lib.MAX_ARMS:
+        raise ValueError(f"n_arms must be in [1, {_lib.MAX_ARMS}]")
+    R = int(n_replicates)
+    if not 1 <= R <= _lib.BOOT_MAX_REPLICATES:
+        raise ValueError(f"n_replicates must be in [1, {_lib.BOOT_MAX_REPLICATES}]")
+    if not 0 <= int(seed) < 2 ** 32:
+        raise ValueError("seed must be a uint32")
+    if int(patient_offset) < 0:
+        raise ValueError("patient_offset must be >= 0")
+    F = lib.n_terms
+    dev = mom.device
+    ws = _ws(workspace, dev, "disc").get(L.insite_bootstrap_workspace_bytes(N, n_arms, F, R), dev)
+    tab = lib.ctypes_table()
+    head = (_p(mom), _p(u) if lib.n_statics else ctypes.c_void_p(0), _p(arm), _p(rows), int(min_rows), N,
+            int(patient_offset), lib.n_statics, n_arms, tab.ctypes.data_as(ctypes.c_void_p), F, R, int(seed))
+    n_out = 2 if fit_args is None else 5
+    if out is None:
+        out = (torch.zeros((R, n_arms, F, F), dtype=torch.float64, device=dev),
+               torch.zeros((R, n_arms, F), dtype=torch.float64, device=dev))
+        if fit_args is not None:
+            out = (torch.zeros((R, n_arms, F), dtype=torch.float64, device=dev),
+                   torch.zeros((R, n_arms, F), dtype=torch.int8, device=dev),
+                   torch.zeros((R, n_arms), dtype=torch.int32, device=dev)) + out
+    if len(out) != n_out:
+        raise ValueError(f"out must hold {n_out} tensors")
+    for t, shape in zip(out[-2:], ((R, n_arms, F, F), (R, n_arms, F))):
+        _dev("out", t, torch.float64)
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError("G / b outputs must be contiguous [R, n_arms, F, F] / [R, n_arms, F]")
+    keep = (mom, u, arm, rows, tab, ws, *out)
+    if fit_args is None:
+        G, b = out
+        return "insite_bootstrap_gram_f64", head + (_p(G), _p(b), _p(ws), ws.numel()), dev, out, keep
+    optimizer, threshold, alpha, nu, tol, max_iter, unbias = fit_args
+    if optimizer not in WEAK_OPTIMIZERS:
+        raise ValueError(f"optimizer must be one of {sorted(WEAK_OPTIMIZERS)}")
+    coef, mask, iters, G, b = out
+    if (tuple(coef.shape) != (R, n_arms, F) or tuple(mask.shape) != (R, n_arms, F) or iters.numel() != R * n_arms
+            or not (coef.is_contiguous() and mask.is_contiguous() and iters.is_contiguous())):
+        raise ValueError("coef / mask / iters outputs must be contiguous [R, n_arms, F] / [R, n_arms, F] / [R, n_arms]")
+    _dev("coef", coef, torch.float64)
+    _dev("mask", mask, torch.int8)
+    _dev("iters", iters, torch.int32)
+    args = head + (WEAK_OPTIMIZERS[optimizer], float(threshold), float(alpha), float(nu), float(tol), int(max_iter),
+                   int(bool(unbias)), _p(G), _p(b), _p(coef), _p(mask), _p(iters), _p(ws), ws.numel())
+    return "insite_sindy_bootstrap_f64", args, dev, out, keep
+
+
+def bootstrap_gram(mom: torch.Tensor, u: torch.Tensor, arm: torch.Tensor, rows: torch.Tensor | None,
+                   lib: PolyLibrary, n_replicates: int, seed: int = 0, n_arms: int = 2, min_rows: int = 0,
+                   patient_offset: int = 0, workspace: Workspace | None = None, out: tuple | None = None):
+    """The Gram systems of ``n_replicates`` patient-level Poisson bootstrap replicates from the per-patient moments
+    [N, 5] of a Gram pass (insite_bootstrap_gram_f64; ``gram_moments``, ``gram_irregular`` and ``gram_weak`` write
+    that layout).  Replicate 0 carries weight 1 for every patient (the point estimate); a patient contributes to its
+    arm iff the arm is in [0, n_arms) and (``rows`` is None or rows >= ``min_rows``).  ``patient_offset``: the index
+    of patient 0 in the whole cohort (a shard then draws the weights it has there).  Returns (G[R,A,F,F], b[R,A,F])."""
+    return _run(_prep_bootstrap(mom, u, arm, rows, lib, n_replicates, seed, n_arms, min_rows, patient_offset,
+                                workspace, out))
+
+
+def sindy_bootstrap(mom: torch.Tensor, u: torch.Tensor, arm: torch.Tensor, rows: torch.Tensor | None,
+                    lib: PolyLibrary, n_replicates: int, threshold: float, optimizer: str = "stlsq",
+                    alpha: float = 0.5, nu: float = 1.0, tol: float = 1e-1, max_iter: int = 100, unbias: bool = True,
+                    seed: int = 0, n_arms: int = 2, min_rows: int = 0, patient_offset: int = 0,
+                    workspace: Workspace | None = None, out: tuple | None = None):
+    """``bootstrap_gram`` followed on the stream by the solve of the R n_arms systems (insite_sindy_bootstrap_f64),
+    ``optimizer`` "stlsq" (threshold, alpha) or "sr3" (threshold, nu, tol).  Returns (coef[R,A,F], mask[R,A,F],
+    iters[R,A], G[R,A,F,F], b[R,A,F])."""
+    return _run(_prep_bootstrap(mom, u, arm, rows, lib, n_replicates, seed, n_arms, min_rows, patient_offset,
+                                workspace, out, (optimizer, threshold, alpha, nu, tol, max_iter, unbias)))
+
+
+def plan_bootstrap_gram(mom, u, arm, rows, lib, n_replicates, seed=0, n_arms=2, min_rows=0, patient_offset=0,
+                        workspace=None, out=None) -> Plan:
+    """``bootstrap_gram`` as a prepared launch; ``plan.out`` = (G, b)."""
+    name, args, dev, out, keep = _prep_bootstrap(mom, u, arm, rows, lib, n_replicates, seed, n_arms, min_rows,
+                                                 patient_offset, _plan_ws(workspace), out)
+    return Plan(name, args, dev, out, keep)
+
+
+def plan_sindy_bootstrap(mom, u, arm, rows, lib, n_replicates, threshold, optimizer="stlsq", alpha=0.5, nu=1.0,
+                         tol=1e-1, max_iter=100, unbias=True, seed=0, n_arms=2, min_rows=0, patient_offset=0,
+                         workspace=None, out=None) -> Plan:
+    """``sindy_bootstrap`` as a prepared launch; ``plan.out`` = (coef, mask, iters, G, b)."""
+    name, args, dev, out, keep = _prep_bootstrap(mom, u, arm, rows, lib, n_replicates, seed, n_arms, min_rows,
+                                                 patient_offset, _plan_ws(workspace), out,
+                                                 (optimizer, threshold, alpha, nu, tol, max_iter, unbias))
+    return Plan(name, args, dev, out, keep)
+
+
 GEN_FD_KINDS = {"smoothed4": _lib.FD_SMOOTHED4, "order4": _lib.FD_ORDER4, "order1": _lib.FD_ORDER1,
                 "smoothed1": _lib.FD_SMOOTHED1}
 

@@ -31,7 +31,9 @@ inputs switch on; the degree-4 library runs the state-polynomial refinement kern
 on the treatment-segment datasets runs ``insite_gen_gram_segments_f64`` (per-arm power moments of the
 segment rows).  Weak SINDy (the reference's ``wsindy`` backbone: WeakPDELibrary(K=100) + SR3) runs through the
 model key ``weak_form`` (``fit_weak``: ``insite_sindy_fit_weak_f64``); the key ``wsindy: true``
-itself still raises ``NotImplementedError``.
+itself still raises ``NotImplementedError``.  ``bootstrap`` / ``bootstrap_irregular`` refit the per-arm model on
+patient-level Poisson resamples from the per-patient moments (``insite_sindy_bootstrap_f64``) and
+``predict_interval`` turns the replicates into pointwise prediction bands.
 """
 from __future__ import annotations
 
@@ -40,7 +42,7 @@ import logging
 import numpy as np
 import torch
 
-from . import ops, weak
+from . import bootstrap, ops, weak
 from .library import polynomial_library
 
 logger = logging.getLogger(__name__)
@@ -412,6 +414,93 @@ class SINDY:
         if self._coef_dev is None:
             raise RuntimeError("fit() first")
         return ops.rollout_rk45(y0, u, arm_bits, t_obs, n_obs, self._coef_dev, self._roll_library, **kwargs)
+
+    # ------------------------------------------------------------------ patient-level bootstrap
+    IRREGULAR_WINDOW = {"nonuniform2": 3, "nonuniform4": 5}   # samples the Lagrange derivative needs
+
+    def _check_bootstrap(self, what):
+        if self.joint_model or self.segment_mode or self.library.state_degree > 1:
+            raise NotImplementedError(f"{what} covers the per-arm EQ_4 model over the affine library (not the "
+                                      "joint, treatment-segment or degree-4 modes)")
+
+    def _bootstrap_moments(self, mom, u, arm, rows, min_rows, n_replicates, seed, quantiles, optimizer, max_iter):
+        """The replicates' fits from per-patient moments with the model's own solver parameters -> bootstrap_."""
+        coef, mask, iters, _, _ = ops.sindy_bootstrap(mom, u, arm, rows, self.library, n_replicates,
+                                                      self.sindy_threshold, optimizer=optimizer,
+                                                      alpha=self.sindy_alpha, max_iter=max_iter, unbias=True,
+                                                      seed=seed, n_arms=self.dim_treatments, min_rows=min_rows)
+        self.bootstrap_ = bootstrap.summarize(coef, mask, quantiles, seed=int(seed))
+        self.bootstrap_iters_ = iters
+        return self.bootstrap_
+
+    def bootstrap(self, train_f, n_replicates=256, seed=0, quantiles=(0.025, 0.5, 0.975)):
+        """Patient-level Poisson bootstrap of the discovery (insite_sindy_bootstrap_f64): ``n_replicates`` refits of
+        the model's own regression -- the strong form (``ops.gram_moments``' per-patient moments, STLSQ) or, under
+        ``weak_form``, the weak form (the weak pass's moments, ``weak_optimizer``) -- each on the cohort with every
+        patient weighted by a Poisson(1) count; replicate 0 has weight 1 everywhere (the fit itself).  Stores and
+        returns ``self.bootstrap_`` (``bootstrap.BootstrapResult``); the fitted model is not touched.  Under
+        ``weak_form`` the subdomain centres are drawn as ``fit`` draws them: they are the fitted model's only with a
+        fixed ``weak_seed``."""
+        self._check_bootstrap("bootstrap")
+        self.prepare_data()
+        x, u, arm, rows = self.de_format(train_f)
+        if self.weak_form:
+            T = int(rows.max().item())
+            if T < 2:
+                raise ValueError("the weak form needs trajectories of at least 2 rows")
+            centres = np.sort(weak.draw_centres(T, self.dt, self.weak_K, self.weak_seed))
+            W, D = weak.test_function_weights(T, self.dt, centres, p=self.weak_p, device=self.device)
+            mom = ops.gram_weak(x[:, :T], W, D, u, arm, rows, self.library, n_arms=self.dim_treatments,
+                                moments=True)[2]
+            return self._bootstrap_moments(mom, u, arm, rows, T, n_replicates, seed, quantiles, self.weak_optimizer,
+                                           1000)
+        if int(rows.min().item()) < 5:
+            raise ValueError("a training trajectory has fewer than 5 rows: the savgol(5, 3) smoother "
+                             "and the 5-point derivative need at least 5 samples")
+        mom = ops.gram_moments(x, u, arm, rows, self.dt, self.library, n_arms=self.dim_treatments, fd="smoothed4")[5]
+        return self._bootstrap_moments(mom, u, arm, rows, 5, n_replicates, seed, quantiles, "stlsq", 100)
+
+    def bootstrap_irregular(self, x, t_obs, n_obs, u, arm, fd="nonuniform4", validate=True, n_replicates=256, seed=0,
+                            quantiles=(0.025, 0.5, 0.975)):
+        """``bootstrap`` on the irregular pass's per-patient moments (the arguments of ``fit_irregular``)."""
+        self._check_bootstrap("bootstrap_irregular")
+        mom = ops.gram_irregular(x, t_obs, n_obs, u, arm, self.library, n_arms=self.dim_treatments, fd=fd,
+                                 moments=True, validate=validate)[2]
+        return self._bootstrap_moments(mom, u, arm, n_obs, self.IRREGULAR_WINDOW[fd], n_replicates, seed, quantiles,
+                                       "stlsq", 100)
+
+    def predict_interval(self, dataset, quantiles=(0.025, 0.975), max_rows=1024, return_replicates=False):
+        """Pointwise prediction bands from ``bootstrap_``: the first ``max_rows`` rows of ``dataset`` are rolled out
+        under every replicate's equations (one ``ops.rollout`` with per-row coefficients [n R, n_arms, F], the
+        integrator and the coefficient clean-up of ``get_predictions``) and the quantiles are taken over the
+        replicates 1..R-1.  Returns the standardised band [Q, n, T] (the scale of ``get_predictions``) and, with
+        ``return_replicates``, the rollouts [n, R, T] as well (replicate 0: the point model)."""
+        self._check_bootstrap("predict_interval")
+        bs = getattr(self, "bootstrap_", None)
+        if bs is None:
+            raise RuntimeError("bootstrap() first")
+        R = bs.n_replicates
+        if R < 2:
+            raise ValueError("predict_interval needs at least one resampled replicate (n_replicates >= 2)")
+        d = dataset.data
+        prev, stat, std, mean = self._unscaled_inputs(dataset)
+        n = prev.size(0) if max_rows is None else min(int(max_rows), prev.size(0))
+        T = d["prev_outputs"].shape[1]
+        arm = torch.as_tensor(np.argmax(d["current_treatments"][:n], axis=-1).astype(np.int8), device=self.device)
+        coef = bs.coef.to(self.device)
+        keep = coef.abs() > RHS_COEF_EPS                                   # rhs_coefficients, on the device
+        if self.sindy_quantize:
+            s = 10.0 ** self.sindy_quantize_global_model_round_to
+            coef = torch.round(coef * s) / s
+        coef = torch.where(keep, coef, torch.zeros_like(coef))
+        A, F = coef.shape[1:]
+        y = ops.rollout(prev[:n, 0].repeat_interleave(R).contiguous(), stat[:n].repeat_interleave(R, 0).contiguous(),
+                        arm.repeat_interleave(R, 0).contiguous(), coef.repeat(n, 1, 1).contiguous(), self.library,
+                        self.dt, method=self.integrator, drop_below=0.0, T=T)
+        y = ((y - mean) / std).view(n, R, T)
+        qt = torch.as_tensor([float(v) for v in quantiles], dtype=y.dtype, device=y.device)
+        band = torch.quantile(y[:, 1:], qt, dim=1)
+        return (band, y) if return_replicates else band
 
     # ------------------------------------------------------------------ rollout (A8)
     def _predict_device(self, dataset, tau=1):
