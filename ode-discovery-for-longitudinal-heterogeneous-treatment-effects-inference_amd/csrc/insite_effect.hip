@@ -1,0 +1,534 @@
+// insite_effect.hip — paired treatment-effect bands over the bootstrap ensemble on MI355X (gfx950):
+// include/insite_effect.h, DESIGN.md §9h.
+//
+// Kernel:
+//   effect_bands_kernel   wave = patient.  Lane l holds V = R_pad / 64 replicates (replicate s 64 + l in slot s;
+//                         R_pad = the power of two >= max(64, R)).  Prologue per patient: the affine fold (alpha, beta)
+//                         and the interval map (A_a, B_a) of every replicate and arm, as rollout_tm_kernel.  Per step
+//                         one FMA per replicate and plan (the step's arm is wave-uniform: scalar selects), then per
+//                         series a bitonic network over the R_pad keys in registers -- the stages inside a lane are
+//                         v_min_f64 / v_max_f64, the lane stages DPP moves inside a row of 16 lanes and ds_bpermute
+//                         beyond (no LDS storage, no barrier) -- the order statistics by v_readlane, and mean / std
+//                         by fixed-order wave reductions; a step's three series are sorted together at V <= 4.  The
+//                         [n_series, 3 + Q] results of 16 steps are staged in LDS and flushed as row segments.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <limits>
+
+#include "insite_common.h"
+#include "insite_effect.h"
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------
+// library descriptor (the affine libraries: state exponent <= 1), as insite_boot.hip
+// ---------------------------------------------------------------------------------------------
+struct EfLib {
+  int32_t F, U;
+  int32_t ucode[INSITE_MAX_TERMS];  // column j: eu[j][0] | eu[j][1] << 8 | eu[j][2] << 16 | ex[j] << 24
+};
+
+// the checks and status codes of insite_gram_f64's library validation
+int32_t ef_build_lib(const int8_t* exps, int32_t F, int32_t U, EfLib* lib) {
+  if (!exps || F < 1 || F > INSITE_MAX_TERMS || U < 0 || U > INSITE_MAX_STATICS) return INSITE_E_INVALID_ARG;
+  std::memset(lib, 0, sizeof(*lib));
+  lib->F = F;
+  lib->U = U;
+  for (int j = 0; j < F; ++j) {
+    const int8_t ex = exps[j * (1 + U)];
+    if (ex < 0) return INSITE_E_INVALID_ARG;
+    if (ex > INSITE_MAX_STATE_DEGREE) return INSITE_E_UNSUPPORTED;
+    int c = (int)ex << 24;
+    for (int i = 0; i < U; ++i) {
+      const int8_t e = exps[j * (1 + U) + 1 + i];
+      if (e < 0 || e > 8) return INSITE_E_INVALID_ARG;
+      c |= (int)e << (8 * i);
+    }
+    lib->ucode[j] = c;
+  }
+  return INSITE_OK;
+}
+
+__device__ __forceinline__ double ef_monomial(int code, const double* u) {
+  double m = 1.0;
+#pragma unroll
+  for (int i = 0; i < INSITE_MAX_STATICS; ++i) {
+    const int e = (code >> (8 * i)) & 0xff;
+    for (int k = 0; k < e; ++k) m *= u[i];
+  }
+  return m;
+}
+
+// insite_hip.hip's interval_propagator: one observation interval of either integrator on f(y) = al + be y is the
+// affine map y <- A y + B
+__device__ __forceinline__ void ef_interval_map(int method, int substeps, double h, double al, double be, double& A,
+                                                double& B) {
+  double a1, b1;
+  if (method == INSITE_METHOD_EULER) {
+    a1 = fma(h, be, 1.0);
+    b1 = h * al;
+  } else {
+    const double z = h * be;
+    const double P = fma(z, fma(z, fma(z, 1.0 / 24.0, 1.0 / 6.0), 0.5), 1.0);
+    a1 = fma(z, P, 1.0);
+    b1 = h * al * P;
+  }
+  A = 1.0;
+  B = 0.0;
+  for (int s = 0; s < substeps; ++s) {
+    B = fma(a1, B, b1);
+    A *= a1;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// wave helpers
+// ---------------------------------------------------------------------------------------------
+// the value of lane `src` (wave-uniform), in every lane
+__device__ __forceinline__ double ef_readlane(double v, int src) {
+  const u32x2 w = __builtin_bit_cast(u32x2, v);
+  u32x2 r;
+  r.x = (unsigned)__builtin_amdgcn_readlane((int)w.x, src);
+  r.y = (unsigned)__builtin_amdgcn_readlane((int)w.y, src);
+  return __builtin_bit_cast(double, r);
+}
+
+// the value of the lane whose byte address is `addr` (= 4 x lane)
+__device__ __forceinline__ double ef_permute(double v, int addr) {
+  const u32x2 w = __builtin_bit_cast(u32x2, v);
+  u32x2 r;
+  r.x = (unsigned)__builtin_amdgcn_ds_bpermute(addr, (int)w.x);
+  r.y = (unsigned)__builtin_amdgcn_ds_bpermute(addr, (int)w.y);
+  return __builtin_bit_cast(double, r);
+}
+
+// the value of lane (lane ^ M).  Inside a row of 16 lanes the masks 1, 2, 3, 7, 8 and 15 are DPP moves on the VALU
+// (quad_perm [1,0,3,2], [2,3,0,1], [3,2,1,0], row_half_mirror, row_ror:8, row_mirror); the others go through the LDS
+// crossbar (ds_bpermute_b32, no LDS storage).  Every lane is active wherever this is called.
+template <int M>
+__device__ __forceinline__ double ef_xor_lane(double v, int lane) {
+  constexpr int ctrl = M == 1 ? 0xB1 : M == 2 ? 0x4E : M == 3 ? 0x1B : M == 7 ? 0x141 : M == 8 ? 0x128 : M == 15 ? 0x140 : -1;
+  if constexpr (ctrl >= 0) {
+    const u32x2 w = __builtin_bit_cast(u32x2, v);
+    u32x2 r;
+    r.x = (unsigned)__builtin_amdgcn_update_dpp(0, (int)w.x, ctrl, 0xF, 0xF, true);
+    r.y = (unsigned)__builtin_amdgcn_update_dpp(0, (int)w.y, ctrl, 0xF, 0xF, true);
+    return __builtin_bit_cast(double, r);
+  } else {
+    return ef_permute(v, (lane ^ M) << 2);
+  }
+}
+
+// sums over the wave in a fixed order (xor butterfly: every lane adds the same pairs, so every lane holds the same
+// bits), NB independent sums at a time
+template <int NB, int OFF>
+__device__ __forceinline__ void ef_wave_sum_from(double (&v)[NB], int lane) {
+  if constexpr (OFF < kWave) {
+    double o[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) o[b] = ef_xor_lane<OFF>(v[b], lane);
+#pragma unroll
+    for (int b = 0; b < NB; ++b) v[b] += o[b];
+    ef_wave_sum_from<NB, 2 * OFF>(v, lane);
+  }
+}
+template <int NB>
+__device__ __forceinline__ void ef_wave_sum(double (&v)[NB], int lane) {
+  ef_wave_sum_from<NB, 1>(v, lane);
+}
+
+// Ascending bitonic sort of the 64 V keys of a wave; the key of lane l, slot s has index i = l V + s.  The merge of
+// size k starts with the mirror exchange i <-> i ^ (k - 1) and goes on with i <-> i ^ j, j = k / 4 .. 1, so every
+// compare-exchange puts the minimum at the lower index (no descending runs).  Exchanges inside a lane (j < V) are
+// min / max pairs; an exchange between lanes fetches the partner's key and keeps one of the two.  Keys must not be
+// NaN (the caller replaces NaN by +Inf).
+template <int V>
+constexpr int ef_log2v() { return V == 1 ? 0 : (V == 2 ? 1 : (V == 4 ? 2 : 3)); }
+
+// one compare-exchange i <-> i ^ (1 << JB) of every key of NB independent key sets (every index a template
+// constant: the keys stay in registers; the sets' exchanges are issued together, so the NB dependent chains overlap)
+template <int NB, int V, int JB>
+__device__ __forceinline__ void ef_exchange(double (&key)[NB][V], int lane) {
+  constexpr int LV = ef_log2v<V>();
+  if constexpr (JB < LV) {
+    constexpr int j = 1 << JB;
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+      for (int s = 0; s < V; ++s) {
+        if ((s & j) == 0) {
+          const double lo = __builtin_fmin(key[b][s], key[b][s | j]), hi = __builtin_fmax(key[b][s], key[b][s | j]);
+          key[b][s] = lo;
+          key[b][s | j] = hi;
+        }
+      }
+  } else {
+    constexpr int jl = 1 << (JB - LV);
+    const bool upper = (lane & jl) != 0;
+    double o[NB][V];
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+      for (int s = 0; s < V; ++s) o[b][s] = ef_xor_lane<jl>(key[b][s], lane);
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+      for (int s = 0; s < V; ++s) key[b][s] = ((o[b][s] < key[b][s]) != upper) ? o[b][s] : key[b][s];
+  }
+}
+
+template <int NB, int V, int JB>
+__device__ __forceinline__ void ef_exchanges_down(double (&key)[NB][V], int lane) {
+  if constexpr (JB >= 0) {
+    ef_exchange<NB, V, JB>(key, lane);
+    ef_exchanges_down<NB, V, JB - 1>(key, lane);
+  }
+}
+
+// the merge of size 1 << KB: the mirror exchange, then i <-> i ^ j for j = (1 << KB) / 4 .. 1
+template <int NB, int V, int KB>
+__device__ __forceinline__ void ef_merge(double (&key)[NB][V], int lane) {
+  constexpr int LV = ef_log2v<V>();
+  if constexpr (KB <= LV) {
+    constexpr int m = (1 << KB) - 1;
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+      for (int s = 0; s < V; ++s) {
+        if (s < (s ^ m)) {
+          const double lo = __builtin_fmin(key[b][s], key[b][s ^ m]), hi = __builtin_fmax(key[b][s], key[b][s ^ m]);
+          key[b][s] = lo;
+          key[b][s ^ m] = hi;
+        }
+      }
+  } else {
+    constexpr int lm = (1 << (KB - LV)) - 1;  // partner lane = lane ^ lm, partner slot = V - 1 - s
+    const bool upper = (lane & (1 << (KB - LV - 1))) != 0;
+    double o[NB][V];
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+      for (int s = 0; s < V; ++s) o[b][s] = ef_xor_lane<lm>(key[b][V - 1 - s], lane);
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+      for (int s = 0; s < V; ++s) key[b][s] = ((o[b][s] < key[b][s]) != upper) ? o[b][s] : key[b][s];
+  }
+  ef_exchanges_down<NB, V, KB - 2>(key, lane);
+}
+
+template <int NB, int V, int KB>
+__device__ __forceinline__ void ef_merges_up(double (&key)[NB][V], int lane) {
+  if constexpr (KB <= ef_log2v<V>() + 6) {
+    ef_merge<NB, V, KB>(key, lane);
+    ef_merges_up<NB, V, KB + 1>(key, lane);
+  }
+}
+
+template <int NB, int V>
+__device__ __forceinline__ void ef_sort(double (&key)[NB][V], int lane) {
+  ef_merges_up<NB, V, 1>(key, lane);
+}
+
+// ---------------------------------------------------------------------------------------------
+// effect_bands_kernel
+// ---------------------------------------------------------------------------------------------
+constexpr int kEfTc = 16;                                   // steps staged in LDS between two flushes
+constexpr int kEfMaxStats = 3 + INSITE_EFFECT_MAX_QUANTILES;
+constexpr int kEfMaxBlocks = 1 << 20;                       // blocks of one launch; past it a block walks a run of patients
+
+struct EfArgs {
+  const double* y0;
+  const double* u;
+  const int8_t* arm_a;
+  const int8_t* arm_b;  // nullptr: series A only
+  const double* coef;
+  double* out;
+  int64_t lda, ldb, ldo, N, ppb;  // ppb: patients per block
+  int32_t T, A, substeps, method, R, Q;
+  double dt, drop;
+  // per quantile: i and g of the header's formula (one 16-byte element: a run-time index into a separate int32
+  // array of the kernel argument was copied to scratch)
+  struct Rank {
+    int64_t i;
+    double g;
+  } qr[INSITE_EFFECT_MAX_QUANTILES];
+};
+
+// the sorted key of index i (wave-uniform), in every lane
+template <int V>
+__device__ __forceinline__ double ef_rank_value(const double (&key)[V], int i) {
+  constexpr int LV = ef_log2v<V>();
+  // the slot by a select tree over the bits of i (a chain of slot == s selects, and with V = 2 the one select
+  // between the two keys, is turned into an indexed scratch array: V = 2 selects between the two lane values instead)
+  if constexpr (V == 2) {
+    const double x0 = ef_readlane(key[0], i >> 1), x1 = ef_readlane(key[1], i >> 1);
+    return (i & 1) ? x1 : x0;
+  }
+  double x[V];
+#pragma unroll
+  for (int s = 0; s < V; ++s) x[s] = key[s];
+#pragma unroll
+  for (int b = 0; b < LV; ++b) {
+    const bool odd = ((i >> b) & 1) != 0;
+#pragma unroll
+    for (int s = 0; s < (V >> (b + 1)); ++s) x[s] = odd ? x[2 * s + 1] : x[2 * s];
+  }
+  return ef_readlane(x[0], i >> LV);
+}
+
+// NSER: 1 (plan A only) or 3 series.  The three series of a step are sorted together where the registers allow it
+// (V <= 4: three independent chains of dependent exchanges in flight); V = 8 sorts them one after the other.
+template <int V, int NARM, int NSER>
+__global__ void __launch_bounds__(kWave) effect_bands_kernel(EfArgs ea, EfLib lib) {
+  __shared__ double stage[NSER * kEfMaxStats * kEfTc];
+  constexpr int NB = V <= 4 ? NSER : 1;
+  constexpr int nser = NSER;
+  const int lane = threadIdx.x;
+  const int NS = 3 + ea.Q;
+  const int n = ea.R - 1;
+  const double inf = std::numeric_limits<double>::infinity();
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  const double h = ea.dt / (double)ea.substeps;
+  const int64_t p_lo = (int64_t)blockIdx.x * ea.ppb;
+  const int64_t p_hi = p_lo + ea.ppb < ea.N ? p_lo + ea.ppb : ea.N;
+
+  bool valid[V];  // the slot holds a resampled replicate (1..R-1); replicate 0 is lane 0, slot 0
+#pragma unroll
+  for (int s = 0; s < V; ++s) valid[s] = s * kWave + lane >= 1 && s * kWave + lane < ea.R;
+
+  for (int64_t p = p_lo; p < p_hi; ++p) {
+    // ---- prologue: the interval maps of the lane's replicates -------------------------------------------
+    double uu[INSITE_MAX_STATICS];
+#pragma unroll
+    for (int t = 0; t < INSITE_MAX_STATICS; ++t) uu[t] = t < lib.U ? ea.u[p * lib.U + t] : 0.0;
+    double PA[V][NARM], PB[V][NARM];
+#pragma unroll
+    for (int s = 0; s < V; ++s) {
+      const int r = s * kWave + lane;
+      const double* cb = ea.coef + (int64_t)(r < ea.R ? r : 0) * ea.A * lib.F;
+      double al[NARM], be[NARM];
+#pragma unroll
+      for (int a = 0; a < NARM; ++a) al[a] = be[a] = 0.0;
+#pragma unroll
+      for (int j = 0; j < INSITE_MAX_TERMS; ++j) {
+        if (j < lib.F) {
+          const int code = lib.ucode[j];
+          const double m = ef_monomial(code & 0xffffff, uu);
+          const bool lin = (code >> 24) != 0;
+#pragma unroll
+          for (int a = 0; a < NARM; ++a) {
+            if (a < ea.A) {
+              const double c = cb[a * lib.F + j];
+              // a dropped term adds 0; a NaN coefficient is kept (insite_effect.h)
+              const double v = (fabs(c) > ea.drop || c != c) ? c * m : 0.0;
+              if (lin) be[a] += v;
+              else al[a] += v;
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int a = 0; a < NARM; ++a) ef_interval_map(ea.method, ea.substeps, h, al[a], be[a], PA[s][a], PB[s][a]);
+    }
+    const double y0 = ea.y0[p];
+    double yA[V], yB[V];
+#pragma unroll
+    for (int s = 0; s < V; ++s) yA[s] = yB[s] = y0;
+
+    // ---- time loop -----------------------------------------------------------------------------------------
+    for (int k0 = 0; k0 < ea.T; k0 += kEfTc) {
+      const int nk = ea.T - k0 < kEfTc ? ea.T - k0 : kEfTc;
+      // the chunk's arms: lane i < nk reads step k0 + i (nothing past column T - 1)
+      int wa = 0, wb = 0;
+      if (lane < nk) {
+        wa = ea.arm_a[p * ea.lda + k0 + lane];
+        if (ea.arm_b) wb = ea.arm_b[p * ea.ldb + k0 + lane];
+      }
+      for (int kk = 0; kk < nk; ++kk) {
+        const int aa = __builtin_amdgcn_readlane(wa, kk);
+        const int ab = __builtin_amdgcn_readlane(wb, kk);
+#pragma unroll
+        for (int s = 0; s < V; ++s) {
+          double A = PA[s][0], B = PB[s][0];
+#pragma unroll
+          for (int a = 1; a < NARM; ++a) {
+            A = aa == a ? PA[s][a] : A;
+            B = aa == a ? PB[s][a] : B;
+          }
+          yA[s] = fma(A, yA[s], B);
+        }
+        if (nser == 3) {
+#pragma unroll
+          for (int s = 0; s < V; ++s) {
+            double A = PA[s][0], B = PB[s][0];
+#pragma unroll
+            for (int a = 1; a < NARM; ++a) {
+              A = ab == a ? PA[s][a] : A;
+              B = ab == a ? PB[s][a] : B;
+            }
+            yB[s] = fma(A, yB[s], B);
+          }
+        }
+        // the series, NB at a time (the NB sorts and reductions are independent chains issued together)
+#pragma unroll 1
+        for (int sv0 = 0; sv0 < NSER; sv0 += NB) {
+          double v[NB][V], key[NB][V];
+          bool any_nan[NB];
+#pragma unroll
+          for (int b = 0; b < NB; ++b) {
+            const int sv = sv0 + b;
+            bool bad = false;
+#pragma unroll
+            for (int s = 0; s < V; ++s) {
+              v[b][s] = sv == 0 ? yA[s] : (sv == 1 ? yB[s] : yA[s] - yB[s]);
+              const bool isn = v[b][s] != v[b][s];
+              bad = bad || (valid[s] && isn);
+              key[b][s] = (valid[s] && !isn) ? v[b][s] : inf;
+            }
+            any_nan[b] = __builtin_amdgcn_ballot_w64(bad) != 0;
+          }
+          // mean, shifted by c = v[1] (lane 1, slot 0), and the two-pass standard deviation; fixed order: the lane's
+          // slots ascending, then the wave butterfly
+          double acc[NB], c[NB], mean[NB], sd[NB];
+#pragma unroll
+          for (int b = 0; b < NB; ++b) {
+            c[b] = ef_readlane(v[b][0], 1);
+            c[b] = fabs(c[b]) < inf ? c[b] : 0.0;
+            acc[b] = 0.0;
+#pragma unroll
+            for (int s = 0; s < V; ++s) acc[b] += valid[s] ? v[b][s] - c[b] : 0.0;
+          }
+          ef_wave_sum<NB>(acc, lane);
+#pragma unroll
+          for (int b = 0; b < NB; ++b) {
+            mean[b] = c[b] + acc[b] / (double)n;
+            acc[b] = 0.0;
+#pragma unroll
+            for (int s = 0; s < V; ++s) {
+              const double d = v[b][s] - mean[b];
+              acc[b] += valid[s] ? d * d : 0.0;
+            }
+          }
+          ef_wave_sum<NB>(acc, lane);
+#pragma unroll
+          for (int b = 0; b < NB; ++b) sd[b] = sqrt(acc[b] / (double)(n - 1));
+          ef_sort<NB, V>(key, lane);
+#pragma unroll
+          for (int b = 0; b < NB; ++b) {
+            double* st = stage + ((sv0 + b) * NS) * kEfTc + kk;
+            const double point = ef_readlane(v[b][0], 0);
+            if (lane == 0) {
+              st[0] = point;
+              st[kEfTc] = any_nan[b] ? nan : mean[b];
+              st[2 * kEfTc] = any_nan[b] ? nan : sd[b];
+            }
+            for (int j = 0; j < ea.Q; ++j) {
+              const int i = (int)ea.qr[j].i;
+              const double g = ea.qr[j].g;
+              const double lo = ef_rank_value<V>(key[b], i);
+              const double hi = ef_rank_value<V>(key[b], i + 1 < n ? i + 1 : n - 1);
+              double qv = (g == 0.0 || lo == hi) ? lo : lo + g * (hi - lo);
+              qv = any_nan[b] ? nan : qv;
+              if (lane == 0) st[(3 + j) * kEfTc] = qv;
+            }
+          }
+        }
+      }
+      // ---- flush the chunk: row (series, stat), columns k0 .. k0 + nk - 1 ------------------------------------
+      wave_lds_sync();
+      const int n_el = nser * NS * kEfTc;
+      for (int e = lane; e < n_el; e += kWave) {
+        const int row = e / kEfTc, col = e % kEfTc;
+        if (col < nk) ea.out[((int64_t)row * ea.N + p) * ea.ldo + k0 + col] = stage[e];
+      }
+      wave_lds_sync();
+    }
+  }
+}
+
+template <int V, int NSER>
+void ef_launch_vs(int na, dim3 grid, hipStream_t hs, const EfArgs& ea, const EfLib& lib) {
+  if (na == 1) effect_bands_kernel<V, 1, NSER><<<grid, kWave, 0, hs>>>(ea, lib);
+  else if (na == 2) effect_bands_kernel<V, 2, NSER><<<grid, kWave, 0, hs>>>(ea, lib);
+  else effect_bands_kernel<V, 4, NSER><<<grid, kWave, 0, hs>>>(ea, lib);
+}
+
+template <int V>
+void ef_launch_v(int na, dim3 grid, hipStream_t hs, const EfArgs& ea, const EfLib& lib) {
+  if (ea.arm_b) ef_launch_vs<V, 3>(na, grid, hs, ea, lib);
+  else ef_launch_vs<V, 1>(na, grid, hs, ea, lib);
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t insite_effect_abi_version(void) { return INSITE_EFFECT_ABI_VERSION; }
+
+size_t insite_effect_workspace_bytes(int64_t, int32_t, int32_t, int32_t, int32_t, int32_t) { return 0; }
+
+int32_t insite_effect_bands_f64(const double* y0, const double* u, const int8_t* arm_a, int64_t ld_arm_a,
+                                const int8_t* arm_b, int64_t ld_arm_b, const double* coef, const int8_t* exps,
+                                int32_t n_terms, int64_t n_rows, int32_t T, int32_t n_statics, int32_t n_arms,
+                                double dt, int32_t method, int32_t substeps, double drop_below,
+                                int32_t n_replicates, const double* q, int32_t n_quantiles, double* out,
+                                int64_t ld_out, void* /*workspace*/, size_t /*workspace_bytes*/, void* stream) {
+  if (n_rows < 0 || T < 1 || n_arms < 1 || n_arms > INSITE_MAX_ARMS || substeps < 1 || !(dt >= 0.0) ||
+      ld_arm_a < (int64_t)T || (arm_b && ld_arm_b < (int64_t)T) || ld_out < (int64_t)T || n_replicates < 2 ||
+      n_quantiles < 1 || n_quantiles > INSITE_EFFECT_MAX_QUANTILES || !q)
+    return INSITE_E_INVALID_ARG;
+  for (int j = 0; j < n_quantiles; ++j)
+    if (!(q[j] >= 0.0 && q[j] <= 1.0)) return INSITE_E_INVALID_ARG;  // NaN fails both comparisons
+  if (method != INSITE_METHOD_EULER && method != INSITE_METHOD_RK4) return INSITE_E_UNSUPPORTED;
+  EfLib lib;
+  const int32_t st = ef_build_lib(exps, n_terms, n_statics, &lib);
+  if (st != INSITE_OK) return st;
+  if (n_replicates > INSITE_EFFECT_MAX_REPLICATES) return INSITE_E_UNSUPPORTED;
+  if (n_rows == 0) return INSITE_OK;
+  if (!y0 || !arm_a || !coef || !out || (n_statics > 0 && !u)) return INSITE_E_INVALID_ARG;
+
+  EfArgs ea;
+  std::memset(&ea, 0, sizeof(ea));
+  ea.y0 = y0;
+  ea.u = n_statics > 0 ? u : y0;  // never read
+  ea.arm_a = arm_a;
+  ea.arm_b = arm_b;
+  ea.coef = coef;
+  ea.out = out;
+  ea.lda = ld_arm_a;
+  ea.ldb = arm_b ? ld_arm_b : 0;
+  ea.ldo = ld_out;
+  ea.N = n_rows;
+  ea.T = T;
+  ea.A = n_arms;
+  ea.substeps = substeps;
+  ea.method = method;
+  ea.R = n_replicates;
+  ea.Q = n_quantiles;
+  ea.dt = dt;
+  ea.drop = drop_below;
+  const int n = n_replicates - 1;
+  for (int j = 0; j < n_quantiles; ++j) {
+    const double pos = q[j] * (double)(n - 1);
+    int i = (int)std::floor(pos);
+    if (i > n - 1) i = n - 1;
+    ea.qr[j].i = i;
+    ea.qr[j].g = pos - (double)i;
+  }
+  const int64_t blocks = n_rows < kEfMaxBlocks ? n_rows : kEfMaxBlocks;
+  ea.ppb = (n_rows + blocks - 1) / blocks;
+  const dim3 grid((unsigned)((n_rows + ea.ppb - 1) / ea.ppb));
+  hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
+  const int na = n_arms <= 1 ? 1 : (n_arms <= 2 ? 2 : 4);
+  if (n_replicates <= 64) ef_launch_v<1>(na, grid, hs, ea, lib);
+  else if (n_replicates <= 128) ef_launch_v<2>(na, grid, hs, ea, lib);
+  else if (n_replicates <= 256) ef_launch_v<4>(na, grid, hs, ea, lib);
+  else ef_launch_v<8>(na, grid, hs, ea, lib);
+  return launch_status();
+}
+
+}  // extern "C"

@@ -1,0 +1,44 @@
+"""Result container of the treatment-effect bands (include/insite_effect.h).
+
+The hot path is ``ops.effect_bands``: per row and step, the trajectory under plan A, under plan B and their difference
+A - B (paired within each bootstrap replicate), each with the point model's value and mean, standard deviation and
+quantiles over the replicates 1..R-1.  This module only names the slices of its output.
+"""
+from __future__ import annotations
+
+import dataclasses
+
+import torch
+
+SERIES = ("a", "b", "effect")
+
+
+@dataclasses.dataclass
+class EffectResult:
+    """``series``: the names of the leading dimension, ("a",) or ("a", "b", "effect").  ``point``, ``mean``, ``std``
+    [S, N, T]: the point model (replicate 0) and the mean / standard deviation (n - 1 divisor) over the replicates
+    1..R-1; ``quantiles`` [S, Q, N, T] in the order of ``q``.  ``result["effect"]`` gives one series as a dict."""
+    point: torch.Tensor
+    mean: torch.Tensor
+    std: torch.Tensor
+    quantiles: torch.Tensor
+    q: tuple
+    series: tuple = SERIES
+
+    def __getitem__(self, name: str) -> dict:
+        i = self.series.index(name)
+        return {"point": self.point[i], "mean": self.mean[i], "std": self.std[i], "quantiles": self.quantiles[i]}
+
+
+def from_bands(out: torch.Tensor, q, shift: float = 0.0, scale: float = 1.0) -> EffectResult:
+    """``ops.effect_bands``' out [S, 3 + Q, N, T] as an ``EffectResult`` in the scale (x - shift) / scale: locations of
+    the series a and b are shifted and divided, their standard deviations and every statistic of the effect series
+    (a difference: the shift cancels) are divided only."""
+    S = out.size(0)
+    if S not in (1, 3) or out.dim() != 4 or out.size(1) != 3 + len(q):
+        raise ValueError("out must be [1 or 3, 3 + Q, N, T]")
+    res = out / scale
+    loc = [0, 1] + list(range(3, out.size(1)))      # point, mean and quantiles
+    res[:min(S, 2), loc] = (out[:min(S, 2), loc] - shift) / scale
+    return EffectResult(point=res[:, 0], mean=res[:, 1], std=res[:, 2], quantiles=res[:, 3:],
+                        q=tuple(float(v) for v in q), series=SERIES[:S])

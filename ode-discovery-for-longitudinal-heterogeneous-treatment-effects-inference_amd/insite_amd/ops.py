@@ -884,6 +884,91 @@ def plan_sindy_bootstrap(mom, u, arm, rows, lib, n_replicates, threshold, optimi
     return Plan(name, args, dev, out, keep)
 
 
+def _prep_effect_bands(y0, u, arm_a, arm_b, coef, lib, dt, quantiles, method, substeps, drop_below, T, out, workspace):
+    """Validate the inputs of the effect bands and pack the C arguments (insite_effect.h)."""
+    L = _lib.load()
+    _dev("y0", y0, torch.float64, 1)
+    N = y0.numel()
+    _dev("arm_a", arm_a, torch.int8, 2)
+    T = arm_a.size(1) if T is None else int(T)
+    if T < 1:
+        raise ValueError("T must be >= 1")
+    for name, arm in (("arm_a", arm_a), ("arm_b", arm_b)):
+        if arm is None and name == "arm_b":
+            continue
+        _dev(name, arm, torch.int8, 2)
+        if arm.size(0) != N or arm.size(1) < T:
+            raise ValueError(f"{name} must be [N, >=T]")
+    if lib.n_statics:
+        _dev("u", u, torch.float64, 2)
+        if u.size(0) != N or u.size(1) != lib.n_statics or u.stride(0) != lib.n_statics:
+            raise ValueError("u must be a contiguous [N, n_statics] tensor")
+    _dev("coef", coef, torch.float64, 3)
+    F = lib.n_terms
+    if not coef.is_contiguous() or coef.size(-1) != F:
+        raise ValueError("coef must be a contiguous [R, n_arms, F] tensor")
+    R, A = coef.size(0), coef.size(1)
+    if not 1 <= A <= _lib.MAX_ARMS:
+        raise ValueError(f"n_arms must be in [1, {_lib.MAX_ARMS}]")
+    if not 2 <= R <= _lib.EFFECT_MAX_REPLICATES:
+        raise ValueError(f"n_replicates must be in [2, {_lib.EFFECT_MAX_REPLICATES}] (replicate 0 is the point model)")
+    q = np.ascontiguousarray([float(v) for v in quantiles], dtype=np.float64)
+    if not 1 <= q.size <= _lib.EFFECT_MAX_QUANTILES:
+        raise ValueError(f"between 1 and {_lib.EFFECT_MAX_QUANTILES} quantiles expected")
+    if not bool(np.all((q >= 0.0) & (q <= 1.0))):
+        raise ValueError("quantiles must lie in [0, 1]")
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {sorted(METHODS)}")
+    m, default_sub = METHODS[method]
+    sub = int(substeps or default_sub)
+    dev = y0.device
+    n_series = 1 if arm_b is None else 3
+    shape = (n_series, 3 + q.size, N, T)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=dev)
+        ld_out = T
+    else:
+        _dev("out", out, torch.float64, 4)
+        # the row stride (rows may be padded); the leading dimensions must be dense over it
+        ld_out = out.stride(2) if N > 1 else (out.stride(1) if N == 1 else max(T, out.size(3)))
+        if (tuple(out.shape[:3]) != shape[:3] or out.size(3) < T or ld_out < out.size(3)
+                or (N > 0 and out.stride(1) != N * ld_out)
+                or (N > 0 and n_series > 1 and out.stride(0) != shape[1] * N * ld_out)):
+            raise ValueError(f"out must be {shape} with dense leading dimensions (rows may be padded)")
+    ws_bytes = L.insite_effect_workspace_bytes(N, T, A, F, R, q.size)
+    ws = _ws(workspace, dev, "scratch").get(ws_bytes, dev) if ws_bytes else None
+    tab = lib.ctypes_table()
+    args = (_p(y0), _p(u) if lib.n_statics else ctypes.c_void_p(0), _p(arm_a), arm_a.stride(0), _p(arm_b),
+            arm_b.stride(0) if arm_b is not None else 0, _p(coef), tab.ctypes.data_as(ctypes.c_void_p), F, N, T,
+            lib.n_statics, A, float(dt), m, sub, float(drop_below), R, q.ctypes.data_as(ctypes.c_void_p), q.size,
+            _p(out), ld_out, _p(ws),
+            ws.numel() if ws is not None else 0)
+    return "insite_effect_bands_f64", args, dev, out, (y0, u, arm_a, arm_b, coef, tab, q, ws, out)
+
+
+def effect_bands(y0: torch.Tensor, u: torch.Tensor, arm_a: torch.Tensor, arm_b: torch.Tensor | None,
+                 coef: torch.Tensor, lib: PolyLibrary, dt: float, quantiles, method: str = "euler5",
+                 substeps: int | None = None, drop_below: float = 1e-3, T: int | None = None,
+                 out: torch.Tensor | None = None, workspace: Workspace | None = None):
+    """Paired treatment-effect bands over a bootstrap ensemble (insite_effect_bands_f64).
+
+    y0 [N] f64, u [N, U] f64, arm_a / arm_b int8 [N, >=T] per-step arms of plan A / plan B (``arm_b`` None: plan A
+    only), coef [R, A, F]: replicate 0 the point model, replicates 1..R-1 the resamples (``sindy_bootstrap``).
+    Returns out [n_series, 3 + Q, N, T]: series A (, B, A - B: paired within each replicate); per series the point
+    model's trajectory, then mean, standard deviation (ddof 1) and the ``quantiles`` over the replicates 1..R-1 of
+    ``rollout``'s trajectories.  The replicate trajectories never exist in memory."""
+    return _run(_prep_effect_bands(y0, u, arm_a, arm_b, coef, lib, dt, quantiles, method, substeps, drop_below, T,
+                                   out, workspace))
+
+
+def plan_effect_bands(y0, u, arm_a, arm_b, coef, lib, dt, quantiles, method="euler5", substeps=None, drop_below=1e-3,
+                      T=None, out=None, workspace=None) -> Plan:
+    """``effect_bands`` as a prepared launch; ``plan.out`` = out."""
+    name, args, dev, out, keep = _prep_effect_bands(y0, u, arm_a, arm_b, coef, lib, dt, quantiles, method, substeps,
+                                                    drop_below, T, out, workspace)
+    return Plan(name, args, dev, out, keep)
+
+
 GEN_FD_KINDS = {"smoothed4": _lib.FD_SMOOTHED4, "order4": _lib.FD_ORDER4, "order1": _lib.FD_ORDER1,
                 "smoothed1": _lib.FD_SMOOTHED1}
 

@@ -33,7 +33,9 @@ segment rows).  Weak SINDy (the reference's ``wsindy`` backbone: WeakPDELibrary(
 model key ``weak_form`` (``fit_weak``: ``insite_sindy_fit_weak_f64``); the key ``wsindy: true``
 itself still raises ``NotImplementedError``.  ``bootstrap`` / ``bootstrap_irregular`` refit the per-arm model on
 patient-level Poisson resamples from the per-patient moments (``insite_sindy_bootstrap_f64``) and
-``predict_interval`` turns the replicates into pointwise prediction bands.
+``predict_interval`` turns the replicates into pointwise prediction bands.  ``predict_bands`` and
+``treatment_effect`` give the bands of every row, and of the paired effect of two treatment plans, without
+materialising the replicate trajectories (``insite_effect_bands_f64``).
 """
 from __future__ import annotations
 
@@ -42,7 +44,7 @@ import logging
 import numpy as np
 import torch
 
-from . import bootstrap, ops, weak
+from . import _lib, bootstrap, effect, ops, weak
 from .library import polynomial_library
 
 logger = logging.getLogger(__name__)
@@ -501,6 +503,72 @@ class SINDY:
         qt = torch.as_tensor([float(v) for v in quantiles], dtype=y.dtype, device=y.device)
         band = torch.quantile(y[:, 1:], qt, dim=1)
         return (band, y) if return_replicates else band
+
+    # ------------------------------------------------------------------ effect bands
+    def _effect_coef(self, what):
+        """The replicates' coefficients [R, A, F] with ``predict_interval``'s clean-up (``rhs_coefficients``)."""
+        self._check_bootstrap(what)
+        bs = getattr(self, "bootstrap_", None)
+        if bs is None:
+            raise RuntimeError("bootstrap() first")
+        R = bs.n_replicates
+        if not 2 <= R <= _lib.EFFECT_MAX_REPLICATES:
+            raise ValueError(f"{what} needs 2 <= n_replicates <= {_lib.EFFECT_MAX_REPLICATES} "
+                             f"(replicate 0 is the point model; {_lib.EFFECT_MAX_REPLICATES} is the kernel's cap), "
+                             f"got {R}")
+        coef = bs.coef.to(self.device)
+        keep = coef.abs() > RHS_COEF_EPS
+        if self.sindy_quantize:
+            s = 10.0 ** self.sindy_quantize_global_model_round_to
+            coef = torch.round(coef * s) / s
+        return torch.where(keep, coef, torch.zeros_like(coef)).contiguous()
+
+    def _plan_arms(self, dataset, plan, name):
+        """A treatment plan as per-step arms int8 [N, T]: None (the dataset's own ``current_treatments``), an int
+        (that arm at every step), an int array [N, T] or a one-hot array [N, T, A]."""
+        ct = dataset.data["current_treatments"]
+        N, T, A = ct.shape
+        if plan is None:
+            arm = np.argmax(ct, axis=-1)
+        elif isinstance(plan, (int, np.integer)):
+            arm = np.full((N, T), int(plan))
+        else:
+            arm = plan.detach().cpu().numpy() if isinstance(plan, torch.Tensor) else np.asarray(plan)
+            if arm.shape == (N, T, A):
+                arm = np.argmax(arm, axis=-1)
+            elif arm.shape != (N, T) or not np.issubdtype(arm.dtype, np.integer):
+                raise ValueError(f"{name}: expected None, an int, an int array [{N}, {T}] or a one-hot array "
+                                 f"[{N}, {T}, {A}]")
+        if arm.size and (arm.min() < 0 or arm.max() >= self.dim_treatments):
+            raise ValueError(f"{name}: arms must lie in [0, {self.dim_treatments})")
+        return torch.as_tensor(np.ascontiguousarray(arm.astype(np.int8)), device=self.device)
+
+    def predict_bands(self, dataset, quantiles=(0.025, 0.975)):
+        """``predict_interval`` for every row of ``dataset`` on its factual plan, from ``bootstrap_``: an
+        ``effect.EffectResult`` with the one series "a" -- the point model's prediction, and mean, standard deviation
+        and ``quantiles`` over the replicates 1..R-1 -- standardised like ``get_predictions``.  One launch of
+        ``ops.effect_bands``: the [N, R, T] replicate rollouts never exist in memory."""
+        coef = self._effect_coef("predict_bands")
+        prev, stat, std, mean = self._unscaled_inputs(dataset)
+        arm = self._plan_arms(dataset, None, "plan")
+        out = ops.effect_bands(prev[:, 0].contiguous(), stat, arm, None, coef, self.library, self.dt, quantiles,
+                               method=self.integrator, drop_below=0.0, T=arm.size(1))
+        return effect.from_bands(out, quantiles, shift=mean, scale=std)
+
+    def treatment_effect(self, dataset, plan_b, plan_a=None, quantiles=(0.025, 0.5, 0.975)):
+        """The counterfactual trajectories of every row of ``dataset`` under ``plan_a`` and ``plan_b`` and their
+        difference a - b, paired within each bootstrap replicate (the quantile of the differences is not the
+        difference of the quantiles).  A plan is None (the dataset's own treatments), an int (that arm at every step),
+        an int array [N, T] or a one-hot array [N, T, A].  Returns an ``effect.EffectResult`` with the series "a", "b"
+        and "effect": a and b standardised like ``get_predictions``, the effect divided by the output's standard
+        deviation only."""
+        coef = self._effect_coef("treatment_effect")
+        prev, stat, std, mean = self._unscaled_inputs(dataset)
+        arm_a = self._plan_arms(dataset, plan_a, "plan_a")
+        arm_b = self._plan_arms(dataset, plan_b, "plan_b")
+        out = ops.effect_bands(prev[:, 0].contiguous(), stat, arm_a, arm_b, coef, self.library, self.dt, quantiles,
+                               method=self.integrator, drop_below=0.0, T=arm_a.size(1))
+        return effect.from_bands(out, quantiles, shift=mean, scale=std)
 
     # ------------------------------------------------------------------ rollout (A8)
     def _predict_device(self, dataset, tau=1):
