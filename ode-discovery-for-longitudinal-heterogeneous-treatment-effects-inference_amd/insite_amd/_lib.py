@@ -32,6 +32,9 @@ WEAK_ABI_VERSION, WEAK_MAX_K = 1, 1024     # include/insite_weak.h
 OPT_SR3, OPT_STLSQ = 0, 1
 BOOTSTRAP_ABI_VERSION, BOOT_MAX_REPLICATES = 1, 16384   # include/insite_bootstrap.h
 EFFECT_ABI_VERSION, EFFECT_MAX_REPLICATES, EFFECT_MAX_QUANTILES = 1, 512, 16   # include/insite_effect.h
+# include/insite_cohort.h
+COHORT_ABI_VERSION, COHORT_MAX_REPLICATES, COHORT_MAX_GROUPS, COHORT_MAX_QUANTILES = 1, 4096, 64, 16
+COHORT_WEIGHT_NONE, COHORT_WEIGHT_POISSON = 0, 1
 METHOD_EULER, METHOD_RK4 = 0, 1
 LAYOUT_PATIENT_MAJOR, LAYOUT_TIME_MAJOR, LAYOUT_TIME_MAJOR_BITS, LAYOUT_PATIENT_MAJOR_BITS = 0, 1, 2, 3
 MAX_TERMS, MAX_STATICS, MAX_ARMS, MAX_STATE_DEGREE = 9, 3, 4, 1
@@ -116,6 +119,16 @@ EFFECT_EXPORTS = (
     "insite_effect_abi_version",
     "insite_effect_workspace_bytes",
     "insite_effect_bands_f64",
+)
+
+# the extension header include/insite_cohort.h (same shared library, its own ABI version; a list of its own:
+# the five lists above are pinned by tests)
+COHORT_EXPORTS = (
+    "insite_cohort_abi_version",
+    "insite_cohort_effect_workspace_bytes",
+    "insite_cohort_effect_sums_f64",
+    "insite_cohort_effect_finalize_f64",
+    "insite_cohort_effect_f64",
 )
 
 
@@ -257,6 +270,18 @@ _SIGNATURES = {
     "insite_effect_bands_f64": (_c_i32, [_vp, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _vp, _c_i32, _c_i64, _c_i32, _c_i32,
                                          _c_i32, _c_f64, _c_i32, _c_i32, _c_f64, _c_i32, _vp, _c_i32, _vp, _c_i64,
                                          _vp, _c_size, _vp]),
+    # insite_cohort.h
+    "insite_cohort_abi_version": (_c_i32, []),
+    "insite_cohort_effect_workspace_bytes": (_c_size, [_c_i64, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32]),
+    "insite_cohort_effect_sums_f64": (_c_i32, [_vp, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _vp, _c_i32, _c_i64, _c_i32,
+                                               _c_i32, _c_i32, _c_f64, _c_i32, _c_i32, _c_f64, _c_i32, _vp, _c_i32,
+                                               _c_i32, ctypes.c_uint32, _c_i64, _vp, _c_i64, _vp, _vp, _c_size, _vp]),
+    "insite_cohort_effect_finalize_f64": (_c_i32, [_vp, _c_i64, _vp, _c_i32, _c_i32, _c_i32, _c_i32, _vp, _c_i32, _vp,
+                                                   _c_i64, _vp]),
+    "insite_cohort_effect_f64": (_c_i32, [_vp, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _vp, _c_i32, _c_i64, _c_i32, _c_i32,
+                                          _c_i32, _c_f64, _c_i32, _c_i32, _c_f64, _c_i32, _vp, _c_i32, _c_i32,
+                                          ctypes.c_uint32, _c_i64, _vp, _c_i64, _vp, _vp, _c_i32, _vp, _c_i64, _vp,
+                                          _c_size, _vp]),
 }
 
 
@@ -295,6 +320,9 @@ def load(path: str | None = None):
         v = lib.insite_effect_abi_version()
         if v != EFFECT_ABI_VERSION:
             raise InsiteLibraryError(f"effect ABI version mismatch: library {v}, bindings {EFFECT_ABI_VERSION}")
+        v = lib.insite_cohort_abi_version()
+        if v != COHORT_ABI_VERSION:
+            raise InsiteLibraryError(f"cohort ABI version mismatch: library {v}, bindings {COHORT_ABI_VERSION}")
         if path is None:
             _lib = lib
         return lib

@@ -42,3 +42,39 @@ def from_bands(out: torch.Tensor, q, shift: float = 0.0, scale: float = 1.0) -> 
     res[:min(S, 2), loc] = (out[:min(S, 2), loc] - shift) / scale
     return EffectResult(point=res[:, 0], mean=res[:, 1], std=res[:, 2], quantiles=res[:, 3:],
                         q=tuple(float(v) for v in q), series=SERIES[:S])
+
+
+@dataclasses.dataclass
+class CohortEffectResult:
+    """The cohort / subgroup averages of ``ops.cohort_effect`` (include/insite_cohort.h).  ``series``:
+    ("a",) or ("a", "b", "effect").  ``point``, ``mean``, ``std`` [S, G, T]: per group the point model's weighted mean
+    trajectory and the mean / standard deviation (n - 1 divisor) of the replicates' weighted means; ``quantiles``
+    [S, Q, G, T] in the order of ``q``; ``weight_sum`` [R, G]: the weight every replicate gave every group (0: the
+    replicate drew no row of the group, and the group's statistics are NaN).  ``result["effect"]`` gives one series
+    as a dict."""
+    point: torch.Tensor
+    mean: torch.Tensor
+    std: torch.Tensor
+    quantiles: torch.Tensor
+    weight_sum: torch.Tensor
+    q: tuple
+    series: tuple = SERIES
+
+    def __getitem__(self, name: str) -> dict:
+        i = self.series.index(name)
+        return {"point": self.point[i], "mean": self.mean[i], "std": self.std[i], "quantiles": self.quantiles[i]}
+
+
+def from_cohort(out: torch.Tensor, wsum: torch.Tensor, q, shift: float = 0.0, scale: float = 1.0) -> CohortEffectResult:
+    """``ops.cohort_effect``'s out [G, S, 3 + Q, T] and wsum [R, G] as a ``CohortEffectResult`` in the scale
+    (x - shift) / scale, by ``from_bands``' rule: locations of the series a and b are shifted and divided, their
+    standard deviations and every statistic of the effect series are divided only."""
+    if out.dim() != 4 or out.size(1) not in (1, 3) or out.size(2) != 3 + len(q):
+        raise ValueError("out must be [G, 1 or 3, 3 + Q, T]")
+    S = out.size(1)
+    o = out.permute(1, 2, 0, 3)                     # [S, 3 + Q, G, T]
+    res = o / scale
+    loc = [0, 1] + list(range(3, o.size(1)))        # point, mean and quantiles
+    res[:min(S, 2), loc] = (o[:min(S, 2), loc] - shift) / scale
+    return CohortEffectResult(point=res[:, 0], mean=res[:, 1], std=res[:, 2], quantiles=res[:, 3:], weight_sum=wsum,
+                              q=tuple(float(v) for v in q), series=SERIES[:S])

@@ -969,6 +969,173 @@ def plan_effect_bands(y0, u, arm_a, arm_b, coef, lib, dt, quantiles, method="eul
     return Plan(name, args, dev, out, keep)
 
 
+COHORT_WEIGHTINGS = {"none": _lib.COHORT_WEIGHT_NONE, "poisson": _lib.COHORT_WEIGHT_POISSON}
+
+
+def _cohort_quantiles(quantiles):
+    q = np.ascontiguousarray([float(v) for v in quantiles], dtype=np.float64)
+    if not 1 <= q.size <= _lib.COHORT_MAX_QUANTILES:
+        raise ValueError(f"between 1 and {_lib.COHORT_MAX_QUANTILES} quantiles expected")
+    if not bool(np.all((q >= 0.0) & (q <= 1.0))):
+        raise ValueError("quantiles must lie in [0, 1]")
+    return q
+
+
+def _cohort_stats_out(out, G, n_series, Q, T, dev):
+    """out [G, S, 3 + Q, >=T] (rows may be padded, everything else dense) and its row stride."""
+    S = 1 if n_series == 1 else 3
+    shape = (G, S, 3 + Q, T)
+    if out is None:
+        return torch.empty(shape, dtype=torch.float64, device=dev), T
+    _dev("out", out, torch.float64, 4)
+    if tuple(out.shape[:3]) != shape[:3] or out.size(3) < T:
+        raise ValueError(f"out must be {shape} (rows may be padded)")
+    ld = out.stride(2) if shape[2] > 1 else max(T, out.size(3))
+    if (ld < out.size(3) or (S > 1 and out.stride(1) != shape[2] * ld)
+            or (G > 1 and out.stride(0) != S * shape[2] * ld)):
+        raise ValueError(f"out must be {shape} with dense leading dimensions (rows may be padded)")
+    return out, ld
+
+
+def _prep_cohort(y0, u, arm_a, arm_b, coef, lib, dt, quantiles, group, n_groups, weighting, seed, patient_offset,
+                 method, substeps, drop_below, T, out, workspace, sums_out):
+    """Validate the inputs of the cohort effect and pack the C arguments (insite_cohort.h); ``quantiles`` None: the
+    sums call alone."""
+    L = _lib.load()
+    _dev("y0", y0, torch.float64, 1)
+    N = y0.numel()
+    _dev("arm_a", arm_a, torch.int8, 2)
+    T = arm_a.size(1) if T is None else int(T)
+    if T < 1:
+        raise ValueError("T must be >= 1")
+    for name, arm in (("arm_a", arm_a), ("arm_b", arm_b)):
+        if arm is None and name == "arm_b":
+            continue
+        _dev(name, arm, torch.int8, 2)
+        if arm.size(0) != N or arm.size(1) < T:
+            raise ValueError(f"{name} must be [N, >=T]")
+    if lib.n_statics:
+        _dev("u", u, torch.float64, 2)
+        if u.size(0) != N or u.size(1) != lib.n_statics or u.stride(0) != lib.n_statics:
+            raise ValueError("u must be a contiguous [N, n_statics] tensor")
+    _dev("coef", coef, torch.float64, 3)
+    F = lib.n_terms
+    if not coef.is_contiguous() or coef.size(-1) != F:
+        raise ValueError("coef must be a contiguous [R, n_arms, F] tensor")
+    R, A = coef.size(0), coef.size(1)
+    if not 1 <= A <= _lib.MAX_ARMS:
+        raise ValueError(f"n_arms must be in [1, {_lib.MAX_ARMS}]")
+    if not 2 <= R <= _lib.COHORT_MAX_REPLICATES:
+        raise ValueError(f"n_replicates must be in [2, {_lib.COHORT_MAX_REPLICATES}] (replicate 0 is the point model)")
+    G = int(n_groups)
+    if not 1 <= G <= _lib.COHORT_MAX_GROUPS:
+        raise ValueError(f"n_groups must be in [1, {_lib.COHORT_MAX_GROUPS}]")
+    if group is not None:
+        _dev("group", group, torch.int32, 1)
+        if group.numel() != N:
+            raise ValueError("group must have one entry per row")
+    if weighting not in COHORT_WEIGHTINGS:
+        raise ValueError(f"weighting must be one of {sorted(COHORT_WEIGHTINGS)}")
+    if not 0 <= int(seed) < 2 ** 32:
+        raise ValueError("seed must be a uint32")
+    if int(patient_offset) < 0:
+        raise ValueError("patient_offset must be >= 0")
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {sorted(METHODS)}")
+    m, default_sub = METHODS[method]
+    sub = int(substeps or default_sub)
+    dev = y0.device
+    n_series = 1 if arm_b is None else 2
+    if sums_out is None:
+        sums_out = (torch.zeros((R, G, n_series, T), dtype=torch.float64, device=dev),
+                    torch.zeros((R, G), dtype=torch.float64, device=dev))
+    sums, wsum = sums_out
+    _dev("sums", sums, torch.float64, 4)
+    _dev("wsum", wsum, torch.float64, 2)
+    if tuple(sums.shape) != (R, G, n_series, T) or not sums.is_contiguous():
+        raise ValueError(f"sums must be a contiguous {(R, G, n_series, T)} tensor")
+    if tuple(wsum.shape) != (R, G) or not wsum.is_contiguous():
+        raise ValueError(f"wsum must be a contiguous {(R, G)} tensor")
+    ws_bytes = L.insite_cohort_effect_workspace_bytes(N, T, A, F, R, G)
+    ws = _ws(workspace, dev, "scratch").get(ws_bytes, dev)
+    tab = lib.ctypes_table()
+    head = (_p(y0), _p(u) if lib.n_statics else ctypes.c_void_p(0), _p(arm_a), arm_a.stride(0), _p(arm_b),
+            arm_b.stride(0) if arm_b is not None else 0, _p(coef), tab.ctypes.data_as(ctypes.c_void_p), F, N, T,
+            lib.n_statics, A, float(dt), m, sub, float(drop_below), R, _p(group), G, COHORT_WEIGHTINGS[weighting],
+            int(seed), int(patient_offset), _p(sums), T, _p(wsum))
+    keep = (y0, u, arm_a, arm_b, coef, group, tab, ws, sums, wsum)
+    if quantiles is None:
+        return "insite_cohort_effect_sums_f64", head + (_p(ws), ws.numel()), dev, (sums, wsum), keep
+    q = _cohort_quantiles(quantiles)
+    out, ld_out = _cohort_stats_out(out, G, n_series, q.size, T, dev)
+    args = head + (q.ctypes.data_as(ctypes.c_void_p), q.size, _p(out), ld_out, _p(ws), ws.numel())
+    return "insite_cohort_effect_f64", args, dev, (out, sums, wsum), keep + (q, out)
+
+
+def cohort_effect_sums(y0: torch.Tensor, u: torch.Tensor, arm_a: torch.Tensor, arm_b: torch.Tensor | None,
+                       coef: torch.Tensor, lib: PolyLibrary, dt: float, group: torch.Tensor | None = None,
+                       n_groups: int = 1, weighting: str = "poisson", seed: int = 0, patient_offset: int = 0,
+                       method: str = "euler5", substeps: int | None = None, drop_below: float = 1e-3,
+                       T: int | None = None, out: tuple | None = None, workspace: Workspace | None = None):
+    """The weighted trajectory sums of a cohort or of one shard of it (insite_cohort_effect_sums_f64):
+    (sums [R, G, n_series, T], wsum [R, G]), n_series = 1 without ``arm_b`` else 2 (A, B).  Both are additive over
+    shards (``patient_offset``: the index of row 0 in the whole cohort); ``cohort_effect_finalize`` turns their total
+    into the statistics.  With no rows nothing is written: fresh outputs are zero."""
+    return _run(_prep_cohort(y0, u, arm_a, arm_b, coef, lib, dt, None, group, n_groups, weighting, seed,
+                             patient_offset, method, substeps, drop_below, T, None, workspace, out))
+
+
+def cohort_effect_finalize(sums: torch.Tensor, wsum: torch.Tensor, quantiles, out: torch.Tensor | None = None):
+    """The statistics of the group means from ``cohort_effect_sums``' (all-reduced) arrays
+    (insite_cohort_effect_finalize_f64): out [G, S, 3 + Q, T], S = 1 (A) or 3 (A, B, A - B); per series the point
+    model's mean trajectory, then mean, standard deviation (ddof 1) and the ``quantiles`` over the replicates 1..R-1."""
+    L = _lib.load()
+    _dev("sums", sums, torch.float64, 4)
+    _dev("wsum", wsum, torch.float64, 2)
+    R, G, n_series, T = sums.shape
+    if not sums.is_contiguous() or not wsum.is_contiguous() or tuple(wsum.shape) != (R, G) or n_series not in (1, 2):
+        raise ValueError("sums / wsum must be contiguous [R, G, 1 or 2, T] / [R, G] tensors")
+    if not 2 <= R <= _lib.COHORT_MAX_REPLICATES:
+        raise ValueError(f"n_replicates must be in [2, {_lib.COHORT_MAX_REPLICATES}] (replicate 0 is the point model)")
+    if not 1 <= G <= _lib.COHORT_MAX_GROUPS or T < 1:
+        raise ValueError(f"n_groups must be in [1, {_lib.COHORT_MAX_GROUPS}] and T >= 1")
+    q = _cohort_quantiles(quantiles)
+    out, ld_out = _cohort_stats_out(out, G, n_series, q.size, T, sums.device)
+    st = L.insite_cohort_effect_finalize_f64(_p(sums), T, _p(wsum), R, G, n_series, T,
+                                             q.ctypes.data_as(ctypes.c_void_p), q.size, _p(out), ld_out,
+                                             _stream(sums.device))
+    _lib.check("insite_cohort_effect_finalize_f64", st)
+    return out
+
+
+def cohort_effect(y0: torch.Tensor, u: torch.Tensor, arm_a: torch.Tensor, arm_b: torch.Tensor | None,
+                  coef: torch.Tensor, lib: PolyLibrary, dt: float, quantiles, group: torch.Tensor | None = None,
+                  n_groups: int = 1, weighting: str = "poisson", seed: int = 0, patient_offset: int = 0,
+                  method: str = "euler5", substeps: int | None = None, drop_below: float = 1e-3,
+                  T: int | None = None, out: torch.Tensor | None = None, workspace: Workspace | None = None):
+    """Cohort and subgroup average treatment effects with bootstrap bands (insite_cohort_effect_f64).
+
+    The inputs of ``effect_bands`` plus ``group`` int32 [N] (None: one group; ids outside [0, n_groups) exclude the
+    row) and the ``weighting`` of the averaged rows: "poisson" (the patient weights ``sindy_bootstrap`` drew under
+    ``seed``, ``patient_offset``; replicate 0 weighs every row 1) or "none".  Returns (out [G, S, 3 + Q, T], sums
+    [R, G, n_series, T], wsum [R, G]): per group and series (A, or A, B, A - B paired within each replicate) the point
+    model's weighted mean trajectory, then mean, standard deviation and quantiles of the replicates' weighted means.
+    A replicate that drew no row of a group makes that group's statistics NaN.  With no rows nothing is written."""
+    return _run(_prep_cohort(y0, u, arm_a, arm_b, coef, lib, dt, quantiles, group, n_groups, weighting, seed,
+                             patient_offset, method, substeps, drop_below, T, out, workspace, None))
+
+
+def plan_cohort_effect(y0, u, arm_a, arm_b, coef, lib, dt, quantiles, group=None, n_groups=1, weighting="poisson",
+                       seed=0, patient_offset=0, method="euler5", substeps=None, drop_below=1e-3, T=None, out=None,
+                       workspace=None) -> Plan:
+    """``cohort_effect`` as a prepared launch; ``plan.out`` = (out, sums, wsum)."""
+    ws = workspace.claim("scratch") if workspace is not None else Workspace("scratch")
+    name, args, dev, outs, keep = _prep_cohort(y0, u, arm_a, arm_b, coef, lib, dt, quantiles, group, n_groups,
+                                               weighting, seed, patient_offset, method, substeps, drop_below, T, out,
+                                               ws, None)
+    return Plan(name, args, dev, outs, keep)
+
+
 GEN_FD_KINDS = {"smoothed4": _lib.FD_SMOOTHED4, "order4": _lib.FD_ORDER4, "order1": _lib.FD_ORDER1,
                 "smoothed1": _lib.FD_SMOOTHED1}
 

@@ -505,16 +505,17 @@ class SINDY:
         return (band, y) if return_replicates else band
 
     # ------------------------------------------------------------------ effect bands
-    def _effect_coef(self, what):
-        """The replicates' coefficients [R, A, F] with ``predict_interval``'s clean-up (``rhs_coefficients``)."""
+    def _effect_coef(self, what, cap=_lib.EFFECT_MAX_REPLICATES):
+        """The replicates' coefficients [R, A, F] with ``predict_interval``'s clean-up (``rhs_coefficients``);
+        ``cap``: the replicate cap of the kernel that ``what`` launches."""
         self._check_bootstrap(what)
         bs = getattr(self, "bootstrap_", None)
         if bs is None:
             raise RuntimeError("bootstrap() first")
         R = bs.n_replicates
-        if not 2 <= R <= _lib.EFFECT_MAX_REPLICATES:
-            raise ValueError(f"{what} needs 2 <= n_replicates <= {_lib.EFFECT_MAX_REPLICATES} "
-                             f"(replicate 0 is the point model; {_lib.EFFECT_MAX_REPLICATES} is the kernel's cap), "
+        if not 2 <= R <= cap:
+            raise ValueError(f"{what} needs 2 <= n_replicates <= {cap} "
+                             f"(replicate 0 is the point model; {cap} is the kernel's cap), "
                              f"got {R}")
         coef = bs.coef.to(self.device)
         keep = coef.abs() > RHS_COEF_EPS
@@ -569,6 +570,70 @@ class SINDY:
         out = ops.effect_bands(prev[:, 0].contiguous(), stat, arm_a, arm_b, coef, self.library, self.dt, quantiles,
                                method=self.integrator, drop_below=0.0, T=arm_a.size(1))
         return effect.from_bands(out, quantiles, shift=mean, scale=std)
+
+    # ------------------------------------------------------------------ cohort averages
+    def _groups(self, groups, N):
+        """``groups`` None (one group) or int ids [N] (negative: the row is excluded) -> (int32 device tensor or None,
+        n_groups)."""
+        if groups is None:
+            return None, 1
+        g = groups.detach().cpu().numpy() if isinstance(groups, torch.Tensor) else np.asarray(groups)
+        if g.shape != (N,) or not np.issubdtype(g.dtype, np.integer):
+            raise ValueError(f"groups: expected None or an int array [{N}] of group ids")
+        n_groups = int(g.max()) + 1 if g.size else 1
+        if not 1 <= n_groups <= _lib.COHORT_MAX_GROUPS:
+            raise ValueError(f"groups: ids must lie in [0, {_lib.COHORT_MAX_GROUPS}) with at least one row included "
+                             "(negative ids exclude a row)")
+        g = np.where(g < 0, -1, g).astype(np.int32)
+        return torch.as_tensor(np.ascontiguousarray(g), device=self.device), n_groups
+
+    def average_effect(self, dataset, plan_b, plan_a=None, groups=None, quantiles=(0.025, 0.5, 0.975),
+                       resample="paired", seed=None):
+        """The average over the cohort (ATE) and over subgroups (CATE) of the trajectories under ``plan_a`` and
+        ``plan_b`` and of their difference a - b, with bands from ``bootstrap_``: every replicate averages its own
+        trajectories, so the band is the band of the mean, not the mean of the rows' bands.  Plans are
+        ``treatment_effect``'s.  ``groups``: None (one group) or int ids [N] (``n_groups = max + 1`` <= 64; a
+        negative id excludes the row).  ``resample``: "paired" -- replicate r weighs the rows with the Poisson counts
+        its own refit drew (``bootstrap_.seed``): for the training cohort in its training order; "independent" --
+        Poisson counts under ``seed`` (required, different from ``bootstrap_.seed``): sampling uncertainty of a cohort
+        the bootstrap never saw; None -- every weight 1: model uncertainty only.  Returns an
+        ``effect.CohortEffectResult`` with the series "a", "b" and "effect": a and b standardised like
+        ``get_predictions``, the effect divided by the output's standard deviation only.  One plan alone is
+        ``predict_average``."""
+        if plan_b is None and plan_a is None:
+            raise ValueError("average_effect compares two plans: with both None they are the dataset's own "
+                             "treatments twice; predict_average gives the one series of one plan")
+        return self._cohort_average("average_effect", dataset, plan_a, plan_b, True, groups, quantiles, resample, seed)
+
+    def predict_average(self, dataset, groups=None, plan=None, quantiles=(0.025, 0.5, 0.975), resample="paired",
+                        seed=None):
+        """``average_effect`` for one plan (None: the dataset's own treatments): the one series "a"."""
+        return self._cohort_average("predict_average", dataset, plan, None, False, groups, quantiles, resample, seed)
+
+    def _cohort_average(self, what, dataset, plan_a, plan_b, two, groups, quantiles, resample, seed):
+        coef = self._effect_coef(what, _lib.COHORT_MAX_REPLICATES)
+        bs = self.bootstrap_
+        if resample == "paired":
+            if bs.seed is None:
+                raise ValueError(f"{what}: resample='paired' needs the seed of bootstrap() (bootstrap_.seed is None)")
+            weighting, use_seed = "poisson", int(bs.seed)
+        elif resample == "independent":
+            if seed is None or (bs.seed is not None and int(seed) == int(bs.seed)):
+                raise ValueError(f"{what}: resample='independent' needs a seed, different from bootstrap_.seed")
+            weighting, use_seed = "poisson", int(seed)
+        elif resample is None:
+            weighting, use_seed = "none", 0
+        else:
+            raise ValueError(f"{what}: resample must be 'paired', 'independent' or None")
+        N = dataset.data["current_treatments"].shape[0]
+        group, n_groups = self._groups(groups, N)
+        prev, stat, std, mean = self._unscaled_inputs(dataset)
+        arm_a = self._plan_arms(dataset, plan_a, "plan_a" if two else "plan")
+        arm_b = self._plan_arms(dataset, plan_b, "plan_b") if two else None
+        out, _, wsum = ops.cohort_effect(prev[:, 0].contiguous(), stat, arm_a, arm_b, coef, self.library, self.dt,
+                                         quantiles, group=group, n_groups=n_groups, weighting=weighting,
+                                         seed=use_seed, method=self.integrator, drop_below=0.0, T=arm_a.size(1))
+        return effect.from_cohort(out, wsum, quantiles, shift=mean, scale=std)
 
     # ------------------------------------------------------------------ rollout (A8)
     def _predict_device(self, dataset, tau=1):
