@@ -16,94 +16,9 @@
 #include <cstring>
 
 #include "insite_bootstrap.h"
-#include "insite_common.h"
+#include "insite_affine.h"
 
 namespace {
-
-// ---------------------------------------------------------------------------------------------
-// library descriptor (the affine libraries of insite_gram_f64: state exponent <= 1), as insite_weak.hip
-// ---------------------------------------------------------------------------------------------
-struct BtLib {
-  int32_t F, U, nE;
-  int32_t ucode[INSITE_MAX_TERMS];  // column j: eu[j][0] | eu[j][1] << 8 | eu[j][2] << 16 | ex[j] << 24
-  int8_t ei[64];
-  int8_t ek[64];  // -1 => moment entry b[ei]
-};
-
-// the checks and status codes of insite_gram_f64's library validation
-int32_t bt_build_lib(const int8_t* exps, int32_t F, int32_t U, BtLib* lib) {
-  if (!exps || F < 1 || F > INSITE_MAX_TERMS || U < 0 || U > INSITE_MAX_STATICS) return INSITE_E_INVALID_ARG;
-  std::memset(lib, 0, sizeof(*lib));
-  lib->F = F;
-  lib->U = U;
-  for (int j = 0; j < F; ++j) {
-    const int8_t ex = exps[j * (1 + U)];
-    if (ex < 0) return INSITE_E_INVALID_ARG;
-    if (ex > INSITE_MAX_STATE_DEGREE) return INSITE_E_UNSUPPORTED;
-    int c = (int)ex << 24;
-    for (int i = 0; i < U; ++i) {
-      const int8_t e = exps[j * (1 + U) + 1 + i];
-      if (e < 0 || e > 8) return INSITE_E_INVALID_ARG;
-      c |= (int)e << (8 * i);
-    }
-    lib->ucode[j] = c;
-  }
-  int e = 0;
-  for (int i = 0; i < F; ++i)
-    for (int k = i; k < F; ++k) {
-      lib->ei[e] = (int8_t)i;
-      lib->ek[e] = (int8_t)k;
-      ++e;
-    }
-  for (int i = 0; i < F; ++i) {
-    lib->ei[e] = (int8_t)i;
-    lib->ek[e] = -1;
-    ++e;
-  }
-  lib->nE = e;
-  return INSITE_OK;
-}
-
-__device__ __forceinline__ double bt_monomial(int code, const double* u) {
-  double m = 1.0;
-#pragma unroll
-  for (int i = 0; i < INSITE_MAX_STATICS; ++i) {
-    const int e = (code >> (8 * i)) & 0xff;
-    for (int k = 0; k < e; ++k) m *= u[i];
-  }
-  return m;
-}
-
-// ---------------------------------------------------------------------------------------------
-// weights: Threefry-2x32-20 (the block function of insite_rng.hip) and the Poisson(1) inverse CDF
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void bt_threefry(uint32_t k0, uint32_t k1, uint32_t& a, uint32_t& b) {
-  const uint32_t ks[3] = {k0, k1, k0 ^ k1 ^ 0x1BD11BDAu};
-  constexpr int R[2][4] = {{13, 15, 26, 6}, {17, 29, 16, 24}};
-  a += ks[0];
-  b += ks[1];
-#pragma unroll
-  for (int g = 0; g < 5; ++g) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      a += b;
-      b = __builtin_rotateleft32(b, R[g & 1][i]) ^ a;
-    }
-    a += ks[(g + 1) % 3];
-    b += ks[(g + 2) % 3] + (uint32_t)(g + 1);
-  }
-}
-
-// w = #{k : v >= T_k}, T_k = floor(2^32 sum_{i <= k} e^-1 / i!) (insite_bootstrap.h; tests/test_bootstrap_oracle.py
-// recomputes the list)
-__device__ __forceinline__ int bt_poisson(uint32_t v) {
-  constexpr uint32_t T[12] = {1580030168u, 3160060337u, 3950075421u, 4213413783u, 4279248373u, 4292415291u,
-                              4294609777u, 4294923276u, 4294962463u, 4294966817u, 4294967252u, 4294967292u};
-  int w = 0;
-#pragma unroll
-  for (int k = 0; k < 12; ++k) w += v >= T[k] ? 1 : 0;
-  return w;
-}
 
 // ---------------------------------------------------------------------------------------------
 // boot_gram_kernel
@@ -157,7 +72,7 @@ inline BtPlan bt_plan(int64_t N, int n_arms, int nE, int R) {
 template <int RT, int CT>
 __global__ void __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(2, 2)))
 boot_gram_kernel(const double* __restrict__ mom, const double* __restrict__ u, const int8_t* __restrict__ arm,
-                 const int32_t* __restrict__ rows, int min_rows, int64_t N, int64_t off, int n_arms, BtLib lib,
+                 const int32_t* __restrict__ rows, int min_rows, int64_t N, int64_t off, int n_arms, AffineGramLib lib,
                  uint32_t seed, int R, int ncol, int64_t g0, int64_t nG, int64_t gpw, int64_t rpad, int64_t cpad,
                  double* __restrict__ partial) {
   __shared__ double ps[8 * kBtPs];
@@ -201,8 +116,8 @@ boot_gram_kernel(const double* __restrict__ mom, const double* __restrict__ u, c
 #pragma unroll
       for (int t = 0; t < INSITE_MAX_STATICS; ++t) uu[t] = t < lib.U ? u[pc * lib.U + t] : 0.0;
       double* row = ps + s1 * kBtPs;
-      if (j1 < lib.F) row[j1] = bt_monomial(lib.ucode[j1] & 0xffffff, uu);
-      if (j1 == 0 && lib.F > 8) row[8] = bt_monomial(lib.ucode[8] & 0xffffff, uu);
+      if (j1 < lib.F) row[j1] = monomial_code(lib.ucode[j1] & 0xffffff, uu);
+      if (j1 == 0 && lib.F > 8) row[8] = monomial_code(lib.ucode[8] & 0xffffff, uu);
       if (j1 < 5) row[9 + j1] = mom[pc * 5 + j1];
       if (j1 == 5) row[14] = (double)(on ? arm_p : -1);
       if (j1 == 6) row[15] = 1.0;
@@ -227,9 +142,9 @@ boot_gram_kernel(const double* __restrict__ mom, const double* __restrict__ u, c
       if ((rt0 + rt) * 16 < R) {  // (uniform)
         const uint32_t r = (uint32_t)((rt0 + rt) * 16 + col);
         uint32_t wa = (uint32_t)q, wb = (uint32_t)(q >> 32);
-        bt_threefry(seed, r, wa, wb);
-        const double w0 = r == 0u ? 1.0 : (double)bt_poisson(wa);
-        const double w1 = r == 0u ? 1.0 : (double)bt_poisson(wb);
+        threefry2x32_20(seed, r, wa, wb);
+        const double w0 = r == 0u ? 1.0 : (double)poisson1_weight(wa);
+        const double w1 = r == 0u ? 1.0 : (double)poisson1_weight(wb);
 #pragma unroll
         for (int t = 0; t < CT; ++t) {
           acc[rt][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(w0, bv[0][t], acc[rt][t], 0, 0, 0);
@@ -252,7 +167,7 @@ boot_gram_kernel(const double* __restrict__ mom, const double* __restrict__ u, c
 // thread = (replicate, entry column): the waves' partials in wave order, then the entry to G (both triangles) or b
 __global__ void __launch_bounds__(kBtFinBlock)
 boot_finalize_kernel(const double* __restrict__ partial, int64_t n_px, int64_t rpad, int64_t cpad, int R, int n_arms,
-                     BtLib lib, double* __restrict__ G, double* __restrict__ b) {
+                     AffineGramLib lib, double* __restrict__ G, double* __restrict__ b) {
   const int ncol = n_arms * lib.nE;
   const int64_t idx = (int64_t)blockIdx.x * kBtFinBlock + threadIdx.x;
   if (idx >= (int64_t)R * ncol) return;
@@ -285,8 +200,8 @@ int32_t run_boot_gram(const double* mom, const double* u, const int8_t* arm, con
       n_arms < 1 || n_arms > INSITE_MAX_ARMS || n_replicates < 1)
     return INSITE_E_INVALID_ARG;
   if (n_patients > 0 && (!mom || !arm || (n_statics > 0 && !u))) return INSITE_E_INVALID_ARG;
-  BtLib lib;
-  const int32_t st = bt_build_lib(exps, n_terms, n_statics, &lib);
+  AffineGramLib lib;
+  const int32_t st = build_affine_lib(exps, n_terms, n_statics, &lib);
   if (st != INSITE_OK) return st;
   if (n_replicates > INSITE_BOOT_MAX_REPLICATES) return INSITE_E_UNSUPPORTED;
   if (!workspace || workspace_bytes < insite_bootstrap_workspace_bytes(n_patients, n_arms, n_terms, n_replicates))

@@ -23,120 +23,10 @@
 #include <cstring>
 #include <limits>
 
-#include "insite_common.h"
+#include "insite_affine.h"
 #include "insite_cohort.h"
 
 namespace {
-
-// ---------------------------------------------------------------------------------------------
-// library descriptor, monomials and the interval map, as insite_effect.hip
-// ---------------------------------------------------------------------------------------------
-struct CoLib {
-  int32_t F, U;
-  int32_t ucode[INSITE_MAX_TERMS];  // column j: eu[j][0] | eu[j][1] << 8 | eu[j][2] << 16 | ex[j] << 24
-};
-
-// the checks and status codes of insite_gram_f64's library validation
-int32_t co_build_lib(const int8_t* exps, int32_t F, int32_t U, CoLib* lib) {
-  if (!exps || F < 1 || F > INSITE_MAX_TERMS || U < 0 || U > INSITE_MAX_STATICS) return INSITE_E_INVALID_ARG;
-  std::memset(lib, 0, sizeof(*lib));
-  lib->F = F;
-  lib->U = U;
-  for (int j = 0; j < F; ++j) {
-    const int8_t ex = exps[j * (1 + U)];
-    if (ex < 0) return INSITE_E_INVALID_ARG;
-    if (ex > INSITE_MAX_STATE_DEGREE) return INSITE_E_UNSUPPORTED;
-    int c = (int)ex << 24;
-    for (int i = 0; i < U; ++i) {
-      const int8_t e = exps[j * (1 + U) + 1 + i];
-      if (e < 0 || e > 8) return INSITE_E_INVALID_ARG;
-      c |= (int)e << (8 * i);
-    }
-    lib->ucode[j] = c;
-  }
-  return INSITE_OK;
-}
-
-// the monomial of the statics whose exponents `code` packs (8 bits each): 1 times u[0] e0 times, then u[1], u[2] --
-// the multiplication order of insite_effect.hip.  A patient's monomials are wave-uniform, so lane j computes term j
-// once (the trip counts differ between lanes, not between the terms' turns) and the fold reads it back as a scalar.
-__device__ __forceinline__ double co_monomial(int code, const double* u) {
-  double m = 1.0;
-#pragma unroll
-  for (int i = 0; i < INSITE_MAX_STATICS; ++i) {
-    const int e = (code >> (8 * i)) & 0xff;
-    for (int k = 0; k < e; ++k) m *= u[i];
-  }
-  return m;
-}
-
-// the value of lane `src` (wave-uniform), in every lane
-__device__ __forceinline__ double co_readlane(double v, int src) {
-  const u32x2 w = __builtin_bit_cast(u32x2, v);
-  u32x2 r;
-  r.x = (unsigned)__builtin_amdgcn_readlane((int)w.x, src);
-  r.y = (unsigned)__builtin_amdgcn_readlane((int)w.y, src);
-  return __builtin_bit_cast(double, r);
-}
-
-// insite_hip.hip's interval_propagator: one observation interval of either integrator on f(y) = al + be y is the
-// affine map y <- A y + B; every arm in one pass over the sub-steps
-template <int NARM>
-__device__ __forceinline__ void co_interval_maps(int method, int substeps, double h, const double (&al)[NARM],
-                                                 const double (&be)[NARM], double (&A)[NARM], double (&B)[NARM]) {
-  double a1[NARM], b1[NARM];
-#pragma unroll
-  for (int a = 0; a < NARM; ++a) {
-    if (method == INSITE_METHOD_EULER) {
-      a1[a] = fma(h, be[a], 1.0);
-      b1[a] = h * al[a];
-    } else {
-      const double z = h * be[a];
-      const double P = fma(z, fma(z, fma(z, 1.0 / 24.0, 1.0 / 6.0), 0.5), 1.0);
-      a1[a] = fma(z, P, 1.0);
-      b1[a] = h * al[a] * P;
-    }
-    A[a] = 1.0;
-    B[a] = 0.0;
-  }
-  for (int s = 0; s < substeps; ++s) {
-#pragma unroll
-    for (int a = 0; a < NARM; ++a) {
-      B[a] = fma(a1[a], B[a], b1[a]);
-      A[a] *= a1[a];
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// weights: Threefry-2x32-20 and the Poisson(1) inverse CDF, as insite_boot.hip
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void co_threefry(uint32_t k0, uint32_t k1, uint32_t& a, uint32_t& b) {
-  const uint32_t ks[3] = {k0, k1, k0 ^ k1 ^ 0x1BD11BDAu};
-  constexpr int R[2][4] = {{13, 15, 26, 6}, {17, 29, 16, 24}};
-  a += ks[0];
-  b += ks[1];
-#pragma unroll
-  for (int g = 0; g < 5; ++g) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      a += b;
-      b = __builtin_rotateleft32(b, R[g & 1][i]) ^ a;
-    }
-    a += ks[(g + 1) % 3];
-    b += ks[(g + 2) % 3] + (uint32_t)(g + 1);
-  }
-}
-
-// w = #{k : v >= T_k}, T_k = floor(2^32 sum_{i <= k} e^-1 / i!) (insite_bootstrap.h)
-__device__ __forceinline__ int co_poisson(uint32_t v) {
-  constexpr uint32_t T[12] = {1580030168u, 3160060337u, 3950075421u, 4213413783u, 4279248373u, 4292415291u,
-                              4294609777u, 4294923276u, 4294962463u, 4294966817u, 4294967252u, 4294967292u};
-  int w = 0;
-#pragma unroll
-  for (int k = 0; k < 12; ++k) w += v >= T[k] ? 1 : 0;
-  return w;
-}
 
 // ---------------------------------------------------------------------------------------------
 // launch plan
@@ -247,7 +137,7 @@ struct CoRow {
 // NSER: 1 (plan A only) or 2 plans.  Grid: x = chunk + n_chunks (rt + n_rt (g + G (n_tt - 1 - time tile))): blocks are
 // dispatched in that order, the long time tiles first.
 template <int TT, int NARM, int NSER>
-__global__ void __launch_bounds__(kWave) cohort_sums_kernel(CoArgs ca, CoLib lib) {
+__global__ void __launch_bounds__(kWave) cohort_sums_kernel(CoArgs ca, AffineLib lib) {
   constexpr int kCoTt = TT;
   // the replicate tile's coefficients, transposed: cs[a F + j][lane] (conflict-free column reads)
   __shared__ double cs[NARM * INSITE_MAX_TERMS * kWave];
@@ -334,22 +224,24 @@ __global__ void __launch_bounds__(kWave) cohort_sums_kernel(CoArgs ca, CoLib lib
       if (q != q_have) {  // (uniform)
         wa = (uint32_t)q;
         wb = (uint32_t)(q >> 32);
-        co_threefry(ca.seed, (uint32_t)r, wa, wb);
+        threefry2x32_20(ca.seed, (uint32_t)r, wa, wb);
         q_have = q;
       }
-      w = r == 0 ? 1.0 : (double)co_poisson((gi & 1) ? wb : wa);
+      w = r == 0 ? 1.0 : (double)poisson1_weight((gi & 1) ? wb : wa);
     }
     const bool on = w != 0.0;
     wacc += w;
     // ---- prologue: the interval maps of the lane's replicate --------------------------------------------------
-    const double m_l = co_monomial(code_l, row.uu);
+    // A patient's monomials are wave-uniform, so lane j computes term j once (the trip counts differ between lanes,
+    // not between the terms' turns) and the fold reads it back as a scalar.
+    const double m_l = monomial_code(code_l, row.uu);
     double al[NARM], be[NARM];
 #pragma unroll
     for (int a = 0; a < NARM; ++a) al[a] = be[a] = 0.0;
 #pragma unroll
     for (int j = 0; j < INSITE_MAX_TERMS; ++j) {
       if (j < lib.F) {
-        const double m = co_readlane(m_l, j);
+        const double m = readlane_f64(m_l, j);
         const bool lin = (lib.ucode[j] >> 24) != 0;
 #pragma unroll
         for (int a = 0; a < NARM; ++a) {  // (the arms past n_arms hold zeros and no step selects them)
@@ -364,7 +256,7 @@ __global__ void __launch_bounds__(kWave) cohort_sums_kernel(CoArgs ca, CoLib lib
     // a row the replicate did not draw rolls the zero trajectory of the zero map: a select, so that its y0 and u
     // (NaN or not) reach nothing
     double PA[NARM], PB[NARM];
-    co_interval_maps<NARM>(ca.method, ca.substeps, h, al, be, PA, PB);
+    interval_map(ca.method, ca.substeps, h, al, be, PA, PB);
 #pragma unroll
     for (int a = 0; a < NARM; ++a) {
       PA[a] = on ? PA[a] : 0.0;
@@ -473,10 +365,7 @@ struct CoFinArgs {
   double* out;
   int64_t lds, ldo;
   int32_t R, G, nser, T, Q, rpad;
-  struct Rank {
-    int64_t i;
-    double g;
-  } qr[INSITE_COHORT_MAX_QUANTILES];
+  QuantileRank qr[INSITE_COHORT_MAX_QUANTILES];
 };
 
 // the sum of the threads' values in a fixed order (a tree over red[]); every thread gets it
@@ -582,16 +471,9 @@ int32_t co_check_shape(int64_t n_rows, int32_t T, int32_t n_arms, int32_t n_repl
   return INSITE_OK;
 }
 
-int32_t co_check_q(const double* q, int32_t Q) {
-  if (Q < 1 || Q > INSITE_COHORT_MAX_QUANTILES || !q) return INSITE_E_INVALID_ARG;
-  for (int j = 0; j < Q; ++j)
-    if (!(q[j] >= 0.0 && q[j] <= 1.0)) return INSITE_E_INVALID_ARG;  // NaN fails both comparisons
-  return INSITE_OK;
-}
-
 struct CoSumsCall {
   CoArgs ca;
-  CoLib lib;
+  AffineLib lib;
   CoPlan plan;
   int nser;
   bool empty;  // n_rows = 0
@@ -609,7 +491,7 @@ int32_t co_prepare_sums(const double* y0, const double* u, const int8_t* arm_a, 
       (weighting != INSITE_COHORT_WEIGHT_NONE && weighting != INSITE_COHORT_WEIGHT_POISSON))
     return INSITE_E_INVALID_ARG;
   if (method != INSITE_METHOD_EULER && method != INSITE_METHOD_RK4) return INSITE_E_UNSUPPORTED;
-  const int32_t st = co_build_lib(exps, n_terms, n_statics, &c->lib);
+  const int32_t st = build_affine_lib(exps, n_terms, n_statics, &c->lib);
   if (st != INSITE_OK) return st;
   if (n_replicates > INSITE_COHORT_MAX_REPLICATES) return INSITE_E_UNSUPPORTED;
   c->nser = arm_b ? 2 : 1;
@@ -681,7 +563,8 @@ int32_t co_prepare_finalize(const double* sums, int64_t ld_sums, const double* w
                             int32_t n_series, int32_t T, const double* q, int32_t Q, double* out, int64_t ld_out,
                             CoFinArgs* fa) {
   if (!sums || !wsum || !out || R < 2 || G < 1 || G > INSITE_COHORT_MAX_GROUPS || (n_series != 1 && n_series != 2) ||
-      T < 1 || ld_sums < (int64_t)T || ld_out < (int64_t)T || co_check_q(q, Q) != INSITE_OK)
+      T < 1 || ld_sums < (int64_t)T || ld_out < (int64_t)T ||
+      check_quantiles(q, Q, INSITE_COHORT_MAX_QUANTILES) != INSITE_OK)
     return INSITE_E_INVALID_ARG;
   if (R > INSITE_COHORT_MAX_REPLICATES) return INSITE_E_UNSUPPORTED;
   std::memset(fa, 0, sizeof(*fa));
@@ -698,14 +581,7 @@ int32_t co_prepare_finalize(const double* sums, int64_t ld_sums, const double* w
   int rpad = 2;
   while (rpad < R) rpad <<= 1;
   fa->rpad = rpad;
-  const int n = R - 1;
-  for (int j = 0; j < Q; ++j) {
-    const double pos = q[j] * (double)(n - 1);
-    int i = (int)std::floor(pos);
-    if (i > n - 1) i = n - 1;
-    fa->qr[j].i = i;
-    fa->qr[j].g = pos - (double)i;
-  }
+  for (int j = 0; j < Q; ++j) fa->qr[j] = quantile_rank(q[j], R - 1);
   return INSITE_OK;
 }
 
@@ -767,7 +643,8 @@ int32_t insite_cohort_effect_f64(const double* y0, const double* u, const int8_t
                                  int32_t n_quantiles, double* out, int64_t ld_out, void* workspace,
                                  size_t workspace_bytes, void* stream) {
   // the checks that need no pointer into the cohort first, so that n_rows = 0 is still validated in full
-  if (co_check_q(q, n_quantiles) != INSITE_OK || !out || ld_out < (int64_t)T) return INSITE_E_INVALID_ARG;
+  if (check_quantiles(q, n_quantiles, INSITE_COHORT_MAX_QUANTILES) != INSITE_OK || !out || ld_out < (int64_t)T)
+    return INSITE_E_INVALID_ARG;
   CoSumsCall c;
   int32_t st = co_prepare_sums(y0, u, arm_a, ld_arm_a, arm_b, ld_arm_b, coef, exps, n_terms, n_rows, T, n_statics,
                                n_arms, dt, method, substeps, drop_below, n_replicates, group, n_groups, weighting,

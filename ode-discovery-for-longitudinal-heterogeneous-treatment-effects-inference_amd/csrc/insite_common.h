@@ -1,6 +1,7 @@
 // insite_common.h — device helpers shared by the INSITE HIP translation units (insite_hip.hip: one-state
 // PK/PD path; insite_ms.hip: multi-state path).  Everything lives in an anonymous namespace: each
-// translation unit gets its own internal copy.
+// translation unit gets its own internal copy.  insite_affine.h builds on it: the one place of the affine
+// libraries' checks and descriptors, the bootstrap weight stream and the interval map.
 #pragma once
 #include <hip/hip_runtime.h>
 

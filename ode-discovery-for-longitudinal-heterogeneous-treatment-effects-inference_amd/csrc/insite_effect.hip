@@ -18,84 +18,14 @@
 #include <cstring>
 #include <limits>
 
-#include "insite_common.h"
+#include "insite_affine.h"
 #include "insite_effect.h"
 
 namespace {
 
 // ---------------------------------------------------------------------------------------------
-// library descriptor (the affine libraries: state exponent <= 1), as insite_boot.hip
-// ---------------------------------------------------------------------------------------------
-struct EfLib {
-  int32_t F, U;
-  int32_t ucode[INSITE_MAX_TERMS];  // column j: eu[j][0] | eu[j][1] << 8 | eu[j][2] << 16 | ex[j] << 24
-};
-
-// the checks and status codes of insite_gram_f64's library validation
-int32_t ef_build_lib(const int8_t* exps, int32_t F, int32_t U, EfLib* lib) {
-  if (!exps || F < 1 || F > INSITE_MAX_TERMS || U < 0 || U > INSITE_MAX_STATICS) return INSITE_E_INVALID_ARG;
-  std::memset(lib, 0, sizeof(*lib));
-  lib->F = F;
-  lib->U = U;
-  for (int j = 0; j < F; ++j) {
-    const int8_t ex = exps[j * (1 + U)];
-    if (ex < 0) return INSITE_E_INVALID_ARG;
-    if (ex > INSITE_MAX_STATE_DEGREE) return INSITE_E_UNSUPPORTED;
-    int c = (int)ex << 24;
-    for (int i = 0; i < U; ++i) {
-      const int8_t e = exps[j * (1 + U) + 1 + i];
-      if (e < 0 || e > 8) return INSITE_E_INVALID_ARG;
-      c |= (int)e << (8 * i);
-    }
-    lib->ucode[j] = c;
-  }
-  return INSITE_OK;
-}
-
-__device__ __forceinline__ double ef_monomial(int code, const double* u) {
-  double m = 1.0;
-#pragma unroll
-  for (int i = 0; i < INSITE_MAX_STATICS; ++i) {
-    const int e = (code >> (8 * i)) & 0xff;
-    for (int k = 0; k < e; ++k) m *= u[i];
-  }
-  return m;
-}
-
-// insite_hip.hip's interval_propagator: one observation interval of either integrator on f(y) = al + be y is the
-// affine map y <- A y + B
-__device__ __forceinline__ void ef_interval_map(int method, int substeps, double h, double al, double be, double& A,
-                                                double& B) {
-  double a1, b1;
-  if (method == INSITE_METHOD_EULER) {
-    a1 = fma(h, be, 1.0);
-    b1 = h * al;
-  } else {
-    const double z = h * be;
-    const double P = fma(z, fma(z, fma(z, 1.0 / 24.0, 1.0 / 6.0), 0.5), 1.0);
-    a1 = fma(z, P, 1.0);
-    b1 = h * al * P;
-  }
-  A = 1.0;
-  B = 0.0;
-  for (int s = 0; s < substeps; ++s) {
-    B = fma(a1, B, b1);
-    A *= a1;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
 // wave helpers
 // ---------------------------------------------------------------------------------------------
-// the value of lane `src` (wave-uniform), in every lane
-__device__ __forceinline__ double ef_readlane(double v, int src) {
-  const u32x2 w = __builtin_bit_cast(u32x2, v);
-  u32x2 r;
-  r.x = (unsigned)__builtin_amdgcn_readlane((int)w.x, src);
-  r.y = (unsigned)__builtin_amdgcn_readlane((int)w.y, src);
-  return __builtin_bit_cast(double, r);
-}
-
 // the value of the lane whose byte address is `addr` (= 4 x lane)
 __device__ __forceinline__ double ef_permute(double v, int addr) {
   const u32x2 w = __builtin_bit_cast(u32x2, v);
@@ -250,12 +180,7 @@ struct EfArgs {
   int64_t lda, ldb, ldo, N, ppb;  // ppb: patients per block
   int32_t T, A, substeps, method, R, Q;
   double dt, drop;
-  // per quantile: i and g of the header's formula (one 16-byte element: a run-time index into a separate int32
-  // array of the kernel argument was copied to scratch)
-  struct Rank {
-    int64_t i;
-    double g;
-  } qr[INSITE_EFFECT_MAX_QUANTILES];
+  QuantileRank qr[INSITE_EFFECT_MAX_QUANTILES];  // per quantile: i and g of the header's formula
 };
 
 // the sorted key of index i (wave-uniform), in every lane
@@ -265,7 +190,7 @@ __device__ __forceinline__ double ef_rank_value(const double (&key)[V], int i) {
   // the slot by a select tree over the bits of i (a chain of slot == s selects, and with V = 2 the one select
   // between the two keys, is turned into an indexed scratch array: V = 2 selects between the two lane values instead)
   if constexpr (V == 2) {
-    const double x0 = ef_readlane(key[0], i >> 1), x1 = ef_readlane(key[1], i >> 1);
+    const double x0 = readlane_f64(key[0], i >> 1), x1 = readlane_f64(key[1], i >> 1);
     return (i & 1) ? x1 : x0;
   }
   double x[V];
@@ -277,13 +202,13 @@ __device__ __forceinline__ double ef_rank_value(const double (&key)[V], int i) {
 #pragma unroll
     for (int s = 0; s < (V >> (b + 1)); ++s) x[s] = odd ? x[2 * s + 1] : x[2 * s];
   }
-  return ef_readlane(x[0], i >> LV);
+  return readlane_f64(x[0], i >> LV);
 }
 
 // NSER: 1 (plan A only) or 3 series.  The three series of a step are sorted together where the registers allow it
 // (V <= 4: three independent chains of dependent exchanges in flight); V = 8 sorts them one after the other.
 template <int V, int NARM, int NSER>
-__global__ void __launch_bounds__(kWave) effect_bands_kernel(EfArgs ea, EfLib lib) {
+__global__ void __launch_bounds__(kWave) effect_bands_kernel(EfArgs ea, AffineLib lib) {
   __shared__ double stage[NSER * kEfMaxStats * kEfTc];
   constexpr int NB = V <= 4 ? NSER : 1;
   constexpr int nser = NSER;
@@ -317,7 +242,7 @@ __global__ void __launch_bounds__(kWave) effect_bands_kernel(EfArgs ea, EfLib li
       for (int j = 0; j < INSITE_MAX_TERMS; ++j) {
         if (j < lib.F) {
           const int code = lib.ucode[j];
-          const double m = ef_monomial(code & 0xffffff, uu);
+          const double m = monomial_code(code & 0xffffff, uu);
           const bool lin = (code >> 24) != 0;
 #pragma unroll
           for (int a = 0; a < NARM; ++a) {
@@ -332,7 +257,7 @@ __global__ void __launch_bounds__(kWave) effect_bands_kernel(EfArgs ea, EfLib li
         }
       }
 #pragma unroll
-      for (int a = 0; a < NARM; ++a) ef_interval_map(ea.method, ea.substeps, h, al[a], be[a], PA[s][a], PB[s][a]);
+      for (int a = 0; a < NARM; ++a) interval_map(ea.method, ea.substeps, h, al[a], be[a], PA[s][a], PB[s][a]);
     }
     const double y0 = ea.y0[p];
     double yA[V], yB[V];
@@ -396,7 +321,7 @@ __global__ void __launch_bounds__(kWave) effect_bands_kernel(EfArgs ea, EfLib li
           double acc[NB], c[NB], mean[NB], sd[NB];
 #pragma unroll
           for (int b = 0; b < NB; ++b) {
-            c[b] = ef_readlane(v[b][0], 1);
+            c[b] = readlane_f64(v[b][0], 1);
             c[b] = fabs(c[b]) < inf ? c[b] : 0.0;
             acc[b] = 0.0;
 #pragma unroll
@@ -420,7 +345,7 @@ __global__ void __launch_bounds__(kWave) effect_bands_kernel(EfArgs ea, EfLib li
 #pragma unroll
           for (int b = 0; b < NB; ++b) {
             double* st = stage + ((sv0 + b) * NS) * kEfTc + kk;
-            const double point = ef_readlane(v[b][0], 0);
+            const double point = readlane_f64(v[b][0], 0);
             if (lane == 0) {
               st[0] = point;
               st[kEfTc] = any_nan[b] ? nan : mean[b];
@@ -451,14 +376,14 @@ __global__ void __launch_bounds__(kWave) effect_bands_kernel(EfArgs ea, EfLib li
 }
 
 template <int V, int NSER>
-void ef_launch_vs(int na, dim3 grid, hipStream_t hs, const EfArgs& ea, const EfLib& lib) {
+void ef_launch_vs(int na, dim3 grid, hipStream_t hs, const EfArgs& ea, const AffineLib& lib) {
   if (na == 1) effect_bands_kernel<V, 1, NSER><<<grid, kWave, 0, hs>>>(ea, lib);
   else if (na == 2) effect_bands_kernel<V, 2, NSER><<<grid, kWave, 0, hs>>>(ea, lib);
   else effect_bands_kernel<V, 4, NSER><<<grid, kWave, 0, hs>>>(ea, lib);
 }
 
 template <int V>
-void ef_launch_v(int na, dim3 grid, hipStream_t hs, const EfArgs& ea, const EfLib& lib) {
+void ef_launch_v(int na, dim3 grid, hipStream_t hs, const EfArgs& ea, const AffineLib& lib) {
   if (ea.arm_b) ef_launch_vs<V, 3>(na, grid, hs, ea, lib);
   else ef_launch_vs<V, 1>(na, grid, hs, ea, lib);
 }
@@ -479,13 +404,11 @@ int32_t insite_effect_bands_f64(const double* y0, const double* u, const int8_t*
                                 int64_t ld_out, void* /*workspace*/, size_t /*workspace_bytes*/, void* stream) {
   if (n_rows < 0 || T < 1 || n_arms < 1 || n_arms > INSITE_MAX_ARMS || substeps < 1 || !(dt >= 0.0) ||
       ld_arm_a < (int64_t)T || (arm_b && ld_arm_b < (int64_t)T) || ld_out < (int64_t)T || n_replicates < 2 ||
-      n_quantiles < 1 || n_quantiles > INSITE_EFFECT_MAX_QUANTILES || !q)
+      check_quantiles(q, n_quantiles, INSITE_EFFECT_MAX_QUANTILES) != INSITE_OK)
     return INSITE_E_INVALID_ARG;
-  for (int j = 0; j < n_quantiles; ++j)
-    if (!(q[j] >= 0.0 && q[j] <= 1.0)) return INSITE_E_INVALID_ARG;  // NaN fails both comparisons
   if (method != INSITE_METHOD_EULER && method != INSITE_METHOD_RK4) return INSITE_E_UNSUPPORTED;
-  EfLib lib;
-  const int32_t st = ef_build_lib(exps, n_terms, n_statics, &lib);
+  AffineLib lib;
+  const int32_t st = build_affine_lib(exps, n_terms, n_statics, &lib);
   if (st != INSITE_OK) return st;
   if (n_replicates > INSITE_EFFECT_MAX_REPLICATES) return INSITE_E_UNSUPPORTED;
   if (n_rows == 0) return INSITE_OK;
@@ -511,14 +434,7 @@ int32_t insite_effect_bands_f64(const double* y0, const double* u, const int8_t*
   ea.Q = n_quantiles;
   ea.dt = dt;
   ea.drop = drop_below;
-  const int n = n_replicates - 1;
-  for (int j = 0; j < n_quantiles; ++j) {
-    const double pos = q[j] * (double)(n - 1);
-    int i = (int)std::floor(pos);
-    if (i > n - 1) i = n - 1;
-    ea.qr[j].i = i;
-    ea.qr[j].g = pos - (double)i;
-  }
+  for (int j = 0; j < n_quantiles; ++j) ea.qr[j] = quantile_rank(q[j], n_replicates - 1);
   const int64_t blocks = n_rows < kEfMaxBlocks ? n_rows : kEfMaxBlocks;
   ea.ppb = (n_rows + blocks - 1) / blocks;
   const dim3 grid((unsigned)((n_rows + ea.ppb - 1) / ea.ppb));

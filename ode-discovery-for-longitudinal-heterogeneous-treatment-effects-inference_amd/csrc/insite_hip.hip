@@ -30,11 +30,10 @@
 
 #include "insite_hip.h"
 #include "insite_irregular.h"
-#include "insite_common.h"
+#include "insite_affine.h"
 
 namespace {
 
-constexpr int kMaxEntries = 64;       // Gram + moment entries, one per lane
 constexpr int kGramMaxBlocks = 1024;  // fixed cap -> deterministic reduction order
 constexpr int kPsStride = 17;         // per-patient LDS scratch row (odd -> conflict-free)
 
@@ -100,16 +99,6 @@ struct LibDesc {
   int32_t acode[16];                // atom a: atom_exp[a][0] | [1] << 8 | [2] << 16
 };
 
-// prod_i u[i]^((code >> 8 i) & 0xff): the u-monomial of a packed column / atom code
-__device__ __forceinline__ double monomial_code(int code, const double* u) {
-  double m = 1.0;
-#pragma unroll
-  for (int i = 0; i < INSITE_MAX_STATICS; ++i) {
-    const int e = (code >> (8 * i)) & 0xff;
-    for (int k = 0; k < e; ++k) m *= u[i];
-  }
-  return m;
-}
 __device__ __forceinline__ double monomial(const LibDesc& lib, int j, const double* u) {
   return monomial_code(lib.ucode[j] & 0xffffff, u);
 }
@@ -2246,36 +2235,6 @@ __device__ __forceinline__ void affine_rates_regs(const LibDesc& lib, const doub
   }
 }
 
-// Interval propagator.  Every library of this ABI is affine in the state (INSITE_MAX_STATE_DEGREE
-// 1), so per arm the RHS is f(y) = al + be * y with al, be fixed per patient, and one observation
-// interval of either integrator is an affine map y <- A y + B whose coefficients are loop
-// invariants (the stage arithmetic of the reference scan, hoisted out of the time loop):
-//   Euler, S substeps of h = dt/S (odeint, pkpd/utils.py:68-94): y <- (1 + h be) y + h al, S times;
-//   RK4, S steps: k1..k4 of the linear RHS give y <- R(z) y + h al P(z), z = h be,
-//     R = 1 + z + z^2/2 + z^3/6 + z^4/24,  P = 1 + z/2 + z^2/6 + z^3/24, composed S times.
-// The time loop is then one dependent FMA per step instead of ~10 (the RK4 chain's latency, not
-// HBM, bounded small cohorts: DESIGN.md §5).  Results agree with the stage-by-stage evaluation to
-// fp64 rounding (tests: rtol 1e-11 against the oracle's explicit stages).
-__device__ __forceinline__ void interval_propagator(int method, int substeps, double h, double al, double be,
-                                                    double& A, double& B) {
-  double a1, b1;
-  if (method == INSITE_METHOD_EULER) {
-    a1 = fma(h, be, 1.0);
-    b1 = h * al;
-  } else {
-    const double z = h * be;
-    const double P = fma(z, fma(z, fma(z, 1.0 / 24.0, 1.0 / 6.0), 0.5), 1.0);  // 1 + z/2 + z^2/6 + z^3/24
-    a1 = fma(z, P, 1.0);                                                        // R = 1 + z P
-    b1 = h * al * P;
-  }
-  A = 1.0;
-  B = 0.0;
-  for (int s = 0; s < substeps; ++s) {
-    B = fma(a1, B, b1);
-    A *= a1;
-  }
-}
-
 // Per-lane arm bytes of one 32-step tile, loaded straight from the lane's own row (32 contiguous
 // bytes; AV = bytes per load instruction) through a range-checked buffer descriptor.
 template <int AV, int KT>
@@ -2355,7 +2314,7 @@ __global__ void __launch_bounds__(kBlock) rollout_kernel(RolloutArgs ra, LibDesc
 #ifndef INSITE_ROLLOUT_STAGEWISE
   double PA[NARM], PB[NARM];
 #pragma unroll
-  for (int a = 0; a < NARM; ++a) interval_propagator(METHOD, ra.substeps, h, alpha[a], beta[a], PA[a], PB[a]);
+  for (int a = 0; a < NARM; ++a) interval_map(METHOD, ra.substeps, h, alpha[a], beta[a], PA[a], PB[a]);
   auto step = [&](int a) {
     double A = PA[0], B = PB[0];
 #pragma unroll
@@ -2587,7 +2546,7 @@ __device__ __forceinline__ void rollout_bits_range(const RolloutArgs& ra, const 
     const double h = ra.dt / (double)ra.substeps;
 #ifndef INSITE_ROLLOUT_STAGEWISE
 #pragma unroll
-    for (int a = 0; a < NARM; ++a) interval_propagator(METHOD, ra.substeps, h, al[a], be[a], PA[a], PB[a]);
+    for (int a = 0; a < NARM; ++a) interval_map(METHOD, ra.substeps, h, al[a], be[a], PA[a], PB[a]);
 #else  // ablation: PA / PB carry the rates, every step evaluates the method's stages explicitly
 #pragma unroll
     for (int a = 0; a < NARM; ++a) {
@@ -2864,7 +2823,7 @@ __global__ void __launch_bounds__(kBlock) rollout_tm_kernel(RolloutArgs ra, LibD
 #pragma unroll
   for (int q = 0; q < PPL; ++q)
 #pragma unroll
-    for (int a = 0; a < NARM; ++a) interval_propagator(METHOD, ra.substeps, h, alpha[q][a], beta[q][a], PA[q][a], PB[q][a]);
+    for (int a = 0; a < NARM; ++a) interval_map(METHOD, ra.substeps, h, alpha[q][a], beta[q][a], PA[q][a], PB[q][a]);
   auto step = [&](int q, int a) {
     double A = PA[q][0], B = PB[q][0];
 #pragma unroll
@@ -4166,37 +4125,19 @@ sse_finalize(const double* __restrict__ part, int nblk, int T, double* __restric
 // =============================================================================================
 // host helpers
 // =============================================================================================
+// insite_affine.h's checks, codes and entry list, then the byte-wise exponents and the MFMA plan of this unit's kernels
 int build_lib(const int8_t* exps, int32_t F, int32_t U, LibDesc* lib) {
-  if (!exps || F < 1 || F > INSITE_MAX_TERMS || U < 0 || U > INSITE_MAX_STATICS) return INSITE_E_INVALID_ARG;
   std::memset(lib, 0, sizeof(*lib));
   lib->F = F;
   lib->U = U;
+  const int32_t st = pack_exponents(exps, F, U, lib->ucode);
+  if (st != INSITE_OK) return st;
   for (int j = 0; j < F; ++j) {
-    const int8_t ex = exps[j * (1 + U)];
-    if (ex < 0) return INSITE_E_INVALID_ARG;
-    if (ex > INSITE_MAX_STATE_DEGREE) return INSITE_E_UNSUPPORTED;
-    lib->ex[j] = ex;
-    for (int i = 0; i < U; ++i) {
-      const int8_t e = exps[j * (1 + U) + 1 + i];
-      if (e < 0 || e > 8) return INSITE_E_INVALID_ARG;
-      lib->eu[j][i] = e;
-    }
+    lib->ex[j] = exps[j * (1 + U)];
+    for (int i = 0; i < U; ++i) lib->eu[j][i] = exps[j * (1 + U) + 1 + i];
   }
-  int e = 0;
-  for (int i = 0; i < F; ++i)
-    for (int k = i; k < F; ++k) {
-      lib->ei[e] = (int8_t)i;
-      lib->ek[e] = (int8_t)k;
-      ++e;
-    }
-  lib->nG = e;
-  for (int i = 0; i < F; ++i) {
-    lib->ei[e] = (int8_t)i;
-    lib->ek[e] = -1;
-    ++e;
-  }
-  lib->nE = e;
-  if (e > kMaxEntries) return INSITE_E_UNSUPPORTED;
+  lib->nE = gram_entries(F, lib->ei, lib->ek);
+  lib->nG = lib->nE - F;
   // atoms: distinct u-exponent tuples of the columns
   bool fits = true;
   lib->n_atoms = 0;
@@ -4216,11 +4157,6 @@ int build_lib(const int8_t* exps, int32_t F, int32_t U, LibDesc* lib) {
       }
     }
     lib->col_atom[j] = (int8_t)found;
-  }
-  for (int j = 0; j < F; ++j) {
-    int c = (int)lib->ex[j] << 24;
-    for (int t = 0; t < U; ++t) c |= (int)lib->eu[j][t] << (8 * t);
-    lib->ucode[j] = c;
   }
   // Q columns: (atom of the column index, moment) pairs, deduplicated; the atom of "1" for b
   int one_atom = -1;

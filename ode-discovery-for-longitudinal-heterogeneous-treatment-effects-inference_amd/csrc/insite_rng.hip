@@ -14,28 +14,9 @@
 #include <cstdint>
 
 #include "insite_hip.h"
-#include "insite_common.h"
+#include "insite_affine.h"
 
 namespace {
-
-__device__ __forceinline__ uint32_t rotl32(uint32_t v, int r) { return (v << r) | (v >> (32 - r)); }
-
-__device__ __forceinline__ void threefry2x32_20(uint32_t k0, uint32_t k1, uint32_t& a, uint32_t& b) {
-  const uint32_t ks[3] = {k0, k1, k0 ^ k1 ^ 0x1BD11BDAu};
-  constexpr int R[2][4] = {{13, 15, 26, 6}, {17, 29, 16, 24}};
-  a += ks[0];
-  b += ks[1];
-#pragma unroll
-  for (int g = 0; g < 5; ++g) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      a += b;
-      b = rotl32(b, R[g & 1][i]) ^ a;
-    }
-    a += ks[(g + 1) % 3];
-    b += ks[(g + 2) % 3] + (uint32_t)(g + 1);
-  }
-}
 
 // out[i], i < n: word i of threefry_2x32(key, iota(n)); thread j hashes (j, j + h) with h = ceil(n / 2)
 // (the padded count m / 2; the pad count is 0)

@@ -16,64 +16,12 @@
 #include <cstring>
 
 #include "insite_weak.h"
-#include "insite_common.h"
+#include "insite_affine.h"
 
 namespace {
 
-// ---------------------------------------------------------------------------------------------
-// library descriptor (the affine libraries of insite_gram_f64: state exponent <= 1)
-// ---------------------------------------------------------------------------------------------
+// entries of one arm's system at F = INSITE_MAX_TERMS (AffineGramLib's entry list)
 constexpr int kWkMaxEnt = INSITE_MAX_TERMS * (INSITE_MAX_TERMS + 1) / 2 + INSITE_MAX_TERMS;  // 54 <= one wave
-struct WkLib {
-  int32_t F, U, nE;
-  int32_t ucode[INSITE_MAX_TERMS];  // column j: eu[j][0] | eu[j][1] << 8 | eu[j][2] << 16 | ex[j] << 24
-  int8_t ei[64];
-  int8_t ek[64];  // -1 => moment entry b[ei]
-};
-
-// the checks and status codes of insite_gram_f64's library validation
-int32_t wk_build_lib(const int8_t* exps, int32_t F, int32_t U, WkLib* lib) {
-  if (!exps || F < 1 || F > INSITE_MAX_TERMS || U < 0 || U > INSITE_MAX_STATICS) return INSITE_E_INVALID_ARG;
-  std::memset(lib, 0, sizeof(*lib));
-  lib->F = F;
-  lib->U = U;
-  for (int j = 0; j < F; ++j) {
-    const int8_t ex = exps[j * (1 + U)];
-    if (ex < 0) return INSITE_E_INVALID_ARG;
-    if (ex > INSITE_MAX_STATE_DEGREE) return INSITE_E_UNSUPPORTED;
-    int c = (int)ex << 24;
-    for (int i = 0; i < U; ++i) {
-      const int8_t e = exps[j * (1 + U) + 1 + i];
-      if (e < 0 || e > 8) return INSITE_E_INVALID_ARG;
-      c |= (int)e << (8 * i);
-    }
-    lib->ucode[j] = c;
-  }
-  int e = 0;
-  for (int i = 0; i < F; ++i)
-    for (int k = i; k < F; ++k) {
-      lib->ei[e] = (int8_t)i;
-      lib->ek[e] = (int8_t)k;
-      ++e;
-    }
-  for (int i = 0; i < F; ++i) {
-    lib->ei[e] = (int8_t)i;
-    lib->ek[e] = -1;
-    ++e;
-  }
-  lib->nE = e;
-  return INSITE_OK;
-}
-
-__device__ __forceinline__ double wk_monomial(int code, const double* u) {
-  double m = 1.0;
-#pragma unroll
-  for (int i = 0; i < INSITE_MAX_STATICS; ++i) {
-    const int e = (code >> (8 * i)) & 0xff;
-    for (int k = 0; k < e; ++k) m *= u[i];
-  }
-  return m;
-}
 
 // ---------------------------------------------------------------------------------------------
 // weak_prep_kernel + gram_weak_kernel
@@ -163,8 +111,8 @@ __global__ void __launch_bounds__(kBlock)
 gram_weak_kernel(const double* __restrict__ x, int64_t xsp, int64_t xst, int T, const double* __restrict__ W,
                  const double* __restrict__ D, int64_t ldw, int K, const double* __restrict__ cvec,
                  const int32_t* __restrict__ rng, const double* __restrict__ u, const int8_t* __restrict__ arm,
-                 const int32_t* __restrict__ rows, int64_t N, int n_arms, WkLib lib, double* __restrict__ partial,
-                 double* __restrict__ mom) {
+                 const int32_t* __restrict__ rows, int64_t N, int n_arms, AffineGramLib lib,
+                 double* __restrict__ partial, double* __restrict__ mom) {
   __shared__ double psm[kWavesPerBlock * 16 * kWkPs];
   __shared__ double red[kWavesPerBlock * INSITE_MAX_ARMS * kWave];
   const int tid = threadIdx.x;
@@ -262,7 +210,7 @@ gram_weak_kernel(const double* __restrict__ x, int64_t xsp, int64_t xst, int T, 
 #pragma unroll
       for (int t = 0; t < INSITE_MAX_STATICS; ++t) uu[t] = t < lib.U ? u[pc * lib.U + t] : 0.0;
       double* row = ps + col * kWkPs;
-      for (int j = 0; j < lib.F; ++j) row[j] = wk_monomial(lib.ucode[j] & 0xffffff, uu);
+      for (int j = 0; j < lib.F; ++j) row[j] = monomial_code(lib.ucode[j] & 0xffffff, uu);
       row[9] = S0;
       row[10] = S1;
       row[11] = S2;
@@ -300,8 +248,8 @@ gram_weak_kernel(const double* __restrict__ x, int64_t xsp, int64_t xst, int T, 
 // One block: group sums (kWkGroup consecutive blocks, block order) -> gpart, then the groups in order -> G | b.
 constexpr int kWkFinBlock = 1024;
 __global__ void __launch_bounds__(kWkFinBlock)
-weak_finalize_kernel(const double* __restrict__ part, int nblk, int n_arms, WkLib lib, double* __restrict__ gpart,
-                     double* __restrict__ G, double* __restrict__ b) {
+weak_finalize_kernel(const double* __restrict__ part, int nblk, int n_arms, AffineGramLib lib,
+                     double* __restrict__ gpart, double* __restrict__ G, double* __restrict__ b) {
   const int n_ent = n_arms * lib.nE;
   const int ng = (nblk + kWkGroup - 1) / kWkGroup;
   for (int pi = threadIdx.x; pi < ng * n_ent; pi += kWkFinBlock) {
@@ -469,8 +417,8 @@ inline bool sr3_params_ok(double threshold, double nu, double tol, int32_t max_i
 template <int NARM>
 void launch_gram_weak(hipStream_t hs, int64_t grid, const double* x, int64_t xsp, int64_t xst, int T, const double* W,
                       const double* D, int64_t ldw, int K, const double* cvec, const int32_t* rng, const double* u,
-                      const int8_t* arm, const int32_t* rows, int64_t N, int n_arms, const WkLib& lib, double* part,
-                      double* mom) {
+                      const int8_t* arm, const int32_t* rows, int64_t N, int n_arms, const AffineGramLib& lib,
+                      double* part, double* mom) {
   gram_weak_kernel<NARM><<<dim3((unsigned)grid), kBlock, 0, hs>>>(x, xsp, xst, T, W, D, ldw, K, cvec, rng, u, arm, rows,
                                                                   N, n_arms, lib, part, mom);
 }
@@ -486,8 +434,8 @@ int32_t run_weak_gram(const double* x, int64_t ldx, int32_t layout, int32_t n_st
       ldw < n_steps || (tm ? ldx < n_patients : ldx < n_steps) || ldx < 1)
     return INSITE_E_INVALID_ARG;
   if (n_patients > 0 && (!x || !W || !D || !arm || !rows || (n_statics > 0 && !u))) return INSITE_E_INVALID_ARG;
-  WkLib lib;
-  const int32_t st = wk_build_lib(exps, n_terms, n_statics, &lib);
+  AffineGramLib lib;
+  const int32_t st = build_affine_lib(exps, n_terms, n_statics, &lib);
   if (st != INSITE_OK) return st;
   if (K > INSITE_WEAK_MAX_K) return INSITE_E_UNSUPPORTED;
   if (!workspace || workspace_bytes < insite_gram_weak_workspace_bytes(n_patients, n_arms, n_terms, K))

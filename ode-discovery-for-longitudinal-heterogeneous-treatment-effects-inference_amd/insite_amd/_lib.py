@@ -284,6 +284,16 @@ _SIGNATURES = {
                                           _c_size, _vp]),
 }
 
+# (getter, the version these bindings were written for, the label of the mismatch message)
+_ABI_VERSIONS = (
+    ("insite_abi_version", ABI_VERSION, ""),
+    ("insite_irregular_abi_version", IRREGULAR_ABI_VERSION, "irregular "),
+    ("insite_weak_abi_version", WEAK_ABI_VERSION, "weak "),
+    ("insite_bootstrap_abi_version", BOOTSTRAP_ABI_VERSION, "bootstrap "),
+    ("insite_effect_abi_version", EFFECT_ABI_VERSION, "effect "),
+    ("insite_cohort_abi_version", COHORT_ABI_VERSION, "cohort "),
+)
+
 
 def load(path: str | None = None):
     """Load (once) and return the ctypes handle; raises InsiteLibraryError if unavailable."""
@@ -305,24 +315,10 @@ def load(path: str | None = None):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
-        v = lib.insite_abi_version()
-        if v != ABI_VERSION:
-            raise InsiteLibraryError(f"ABI version mismatch: library {v}, bindings {ABI_VERSION}")
-        v = lib.insite_irregular_abi_version()
-        if v != IRREGULAR_ABI_VERSION:
-            raise InsiteLibraryError(f"irregular ABI version mismatch: library {v}, bindings {IRREGULAR_ABI_VERSION}")
-        v = lib.insite_weak_abi_version()
-        if v != WEAK_ABI_VERSION:
-            raise InsiteLibraryError(f"weak ABI version mismatch: library {v}, bindings {WEAK_ABI_VERSION}")
-        v = lib.insite_bootstrap_abi_version()
-        if v != BOOTSTRAP_ABI_VERSION:
-            raise InsiteLibraryError(f"bootstrap ABI version mismatch: library {v}, bindings {BOOTSTRAP_ABI_VERSION}")
-        v = lib.insite_effect_abi_version()
-        if v != EFFECT_ABI_VERSION:
-            raise InsiteLibraryError(f"effect ABI version mismatch: library {v}, bindings {EFFECT_ABI_VERSION}")
-        v = lib.insite_cohort_abi_version()
-        if v != COHORT_ABI_VERSION:
-            raise InsiteLibraryError(f"cohort ABI version mismatch: library {v}, bindings {COHORT_ABI_VERSION}")
+        for getter, want, label in _ABI_VERSIONS:
+            v = getattr(lib, getter)()
+            if v != want:
+                raise InsiteLibraryError(f"{label}ABI version mismatch: library {v}, bindings {want}")
         if path is None:
             _lib = lib
         return lib

@@ -884,9 +884,18 @@ def plan_sindy_bootstrap(mom, u, arm, rows, lib, n_replicates, threshold, optimi
     return Plan(name, args, dev, out, keep)
 
 
-def _prep_effect_bands(y0, u, arm_a, arm_b, coef, lib, dt, quantiles, method, substeps, drop_below, T, out, workspace):
-    """Validate the inputs of the effect bands and pack the C arguments (insite_effect.h)."""
-    L = _lib.load()
+def _quantiles(quantiles, cap):
+    q = np.ascontiguousarray([float(v) for v in quantiles], dtype=np.float64)
+    if not 1 <= q.size <= cap:
+        raise ValueError(f"between 1 and {cap} quantiles expected")
+    if not bool(np.all((q >= 0.0) & (q <= 1.0))):
+        raise ValueError("quantiles must lie in [0, 1]")
+    return q
+
+
+def _check_ensemble(y0, u, arm_a, arm_b, coef, lib, T, max_replicates):
+    """What the effect bands and the cohort effect check first, in this order: the plans y0 / arm_a / arm_b / T, the
+    statics u and the ensemble coef [R, n_arms, F] with R up to ``max_replicates``.  Returns (N, T, R, A)."""
     _dev("y0", y0, torch.float64, 1)
     N = y0.numel()
     _dev("arm_a", arm_a, torch.int8, 2)
@@ -904,23 +913,30 @@ def _prep_effect_bands(y0, u, arm_a, arm_b, coef, lib, dt, quantiles, method, su
         if u.size(0) != N or u.size(1) != lib.n_statics or u.stride(0) != lib.n_statics:
             raise ValueError("u must be a contiguous [N, n_statics] tensor")
     _dev("coef", coef, torch.float64, 3)
-    F = lib.n_terms
-    if not coef.is_contiguous() or coef.size(-1) != F:
+    if not coef.is_contiguous() or coef.size(-1) != lib.n_terms:
         raise ValueError("coef must be a contiguous [R, n_arms, F] tensor")
     R, A = coef.size(0), coef.size(1)
     if not 1 <= A <= _lib.MAX_ARMS:
         raise ValueError(f"n_arms must be in [1, {_lib.MAX_ARMS}]")
-    if not 2 <= R <= _lib.EFFECT_MAX_REPLICATES:
-        raise ValueError(f"n_replicates must be in [2, {_lib.EFFECT_MAX_REPLICATES}] (replicate 0 is the point model)")
-    q = np.ascontiguousarray([float(v) for v in quantiles], dtype=np.float64)
-    if not 1 <= q.size <= _lib.EFFECT_MAX_QUANTILES:
-        raise ValueError(f"between 1 and {_lib.EFFECT_MAX_QUANTILES} quantiles expected")
-    if not bool(np.all((q >= 0.0) & (q <= 1.0))):
-        raise ValueError("quantiles must lie in [0, 1]")
+    if not 2 <= R <= max_replicates:
+        raise ValueError(f"n_replicates must be in [2, {max_replicates}] (replicate 0 is the point model)")
+    return N, T, R, A
+
+
+def _method(method, substeps):
     if method not in METHODS:
         raise ValueError(f"method must be one of {sorted(METHODS)}")
     m, default_sub = METHODS[method]
-    sub = int(substeps or default_sub)
+    return m, int(substeps or default_sub)
+
+
+def _prep_effect_bands(y0, u, arm_a, arm_b, coef, lib, dt, quantiles, method, substeps, drop_below, T, out, workspace):
+    """Validate the inputs of the effect bands and pack the C arguments (insite_effect.h)."""
+    L = _lib.load()
+    N, T, R, A = _check_ensemble(y0, u, arm_a, arm_b, coef, lib, T, _lib.EFFECT_MAX_REPLICATES)
+    F = lib.n_terms
+    q = _quantiles(quantiles, _lib.EFFECT_MAX_QUANTILES)
+    m, sub = _method(method, substeps)
     dev = y0.device
     n_series = 1 if arm_b is None else 3
     shape = (n_series, 3 + q.size, N, T)
@@ -972,15 +988,6 @@ def plan_effect_bands(y0, u, arm_a, arm_b, coef, lib, dt, quantiles, method="eul
 COHORT_WEIGHTINGS = {"none": _lib.COHORT_WEIGHT_NONE, "poisson": _lib.COHORT_WEIGHT_POISSON}
 
 
-def _cohort_quantiles(quantiles):
-    q = np.ascontiguousarray([float(v) for v in quantiles], dtype=np.float64)
-    if not 1 <= q.size <= _lib.COHORT_MAX_QUANTILES:
-        raise ValueError(f"between 1 and {_lib.COHORT_MAX_QUANTILES} quantiles expected")
-    if not bool(np.all((q >= 0.0) & (q <= 1.0))):
-        raise ValueError("quantiles must lie in [0, 1]")
-    return q
-
-
 def _cohort_stats_out(out, G, n_series, Q, T, dev):
     """out [G, S, 3 + Q, >=T] (rows may be padded, everything else dense) and its row stride."""
     S = 1 if n_series == 1 else 3
@@ -1002,31 +1009,8 @@ def _prep_cohort(y0, u, arm_a, arm_b, coef, lib, dt, quantiles, group, n_groups,
     """Validate the inputs of the cohort effect and pack the C arguments (insite_cohort.h); ``quantiles`` None: the
     sums call alone."""
     L = _lib.load()
-    _dev("y0", y0, torch.float64, 1)
-    N = y0.numel()
-    _dev("arm_a", arm_a, torch.int8, 2)
-    T = arm_a.size(1) if T is None else int(T)
-    if T < 1:
-        raise ValueError("T must be >= 1")
-    for name, arm in (("arm_a", arm_a), ("arm_b", arm_b)):
-        if arm is None and name == "arm_b":
-            continue
-        _dev(name, arm, torch.int8, 2)
-        if arm.size(0) != N or arm.size(1) < T:
-            raise ValueError(f"{name} must be [N, >=T]")
-    if lib.n_statics:
-        _dev("u", u, torch.float64, 2)
-        if u.size(0) != N or u.size(1) != lib.n_statics or u.stride(0) != lib.n_statics:
-            raise ValueError("u must be a contiguous [N, n_statics] tensor")
-    _dev("coef", coef, torch.float64, 3)
+    N, T, R, A = _check_ensemble(y0, u, arm_a, arm_b, coef, lib, T, _lib.COHORT_MAX_REPLICATES)
     F = lib.n_terms
-    if not coef.is_contiguous() or coef.size(-1) != F:
-        raise ValueError("coef must be a contiguous [R, n_arms, F] tensor")
-    R, A = coef.size(0), coef.size(1)
-    if not 1 <= A <= _lib.MAX_ARMS:
-        raise ValueError(f"n_arms must be in [1, {_lib.MAX_ARMS}]")
-    if not 2 <= R <= _lib.COHORT_MAX_REPLICATES:
-        raise ValueError(f"n_replicates must be in [2, {_lib.COHORT_MAX_REPLICATES}] (replicate 0 is the point model)")
     G = int(n_groups)
     if not 1 <= G <= _lib.COHORT_MAX_GROUPS:
         raise ValueError(f"n_groups must be in [1, {_lib.COHORT_MAX_GROUPS}]")
@@ -1040,10 +1024,7 @@ def _prep_cohort(y0, u, arm_a, arm_b, coef, lib, dt, quantiles, group, n_groups,
         raise ValueError("seed must be a uint32")
     if int(patient_offset) < 0:
         raise ValueError("patient_offset must be >= 0")
-    if method not in METHODS:
-        raise ValueError(f"method must be one of {sorted(METHODS)}")
-    m, default_sub = METHODS[method]
-    sub = int(substeps or default_sub)
+    m, sub = _method(method, substeps)
     dev = y0.device
     n_series = 1 if arm_b is None else 2
     if sums_out is None:
@@ -1066,7 +1047,7 @@ def _prep_cohort(y0, u, arm_a, arm_b, coef, lib, dt, quantiles, group, n_groups,
     keep = (y0, u, arm_a, arm_b, coef, group, tab, ws, sums, wsum)
     if quantiles is None:
         return "insite_cohort_effect_sums_f64", head + (_p(ws), ws.numel()), dev, (sums, wsum), keep
-    q = _cohort_quantiles(quantiles)
+    q = _quantiles(quantiles, _lib.COHORT_MAX_QUANTILES)
     out, ld_out = _cohort_stats_out(out, G, n_series, q.size, T, dev)
     args = head + (q.ctypes.data_as(ctypes.c_void_p), q.size, _p(out), ld_out, _p(ws), ws.numel())
     return "insite_cohort_effect_f64", args, dev, (out, sums, wsum), keep + (q, out)
@@ -1099,7 +1080,7 @@ def cohort_effect_finalize(sums: torch.Tensor, wsum: torch.Tensor, quantiles, ou
         raise ValueError(f"n_replicates must be in [2, {_lib.COHORT_MAX_REPLICATES}] (replicate 0 is the point model)")
     if not 1 <= G <= _lib.COHORT_MAX_GROUPS or T < 1:
         raise ValueError(f"n_groups must be in [1, {_lib.COHORT_MAX_GROUPS}] and T >= 1")
-    q = _cohort_quantiles(quantiles)
+    q = _quantiles(quantiles, _lib.COHORT_MAX_QUANTILES)
     out, ld_out = _cohort_stats_out(out, G, n_series, q.size, T, sums.device)
     st = L.insite_cohort_effect_finalize_f64(_p(sums), T, _p(wsum), R, G, n_series, T,
                                              q.ctypes.data_as(ctypes.c_void_p), q.size, _p(out), ld_out,
