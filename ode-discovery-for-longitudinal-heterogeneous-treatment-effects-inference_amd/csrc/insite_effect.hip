@@ -11,6 +11,7 @@
 //                         beyond (no LDS storage, no barrier) -- the order statistics by v_readlane, and mean / std
 //                         by fixed-order wave reductions; a step's three series are sorted together at V <= 4.  The
 //                         [n_series, 3 + Q] results of 16 steps are staged in LDS and flushed as row segments.
+//                         The lane exchanges, sums, sort network and rank reads are insite_wavestats.h's.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -20,148 +21,9 @@
 
 #include "insite_affine.h"
 #include "insite_effect.h"
+#include "insite_wavestats.h"
 
 namespace {
-
-// ---------------------------------------------------------------------------------------------
-// wave helpers
-// ---------------------------------------------------------------------------------------------
-// the value of the lane whose byte address is `addr` (= 4 x lane)
-__device__ __forceinline__ double ef_permute(double v, int addr) {
-  const u32x2 w = __builtin_bit_cast(u32x2, v);
-  u32x2 r;
-  r.x = (unsigned)__builtin_amdgcn_ds_bpermute(addr, (int)w.x);
-  r.y = (unsigned)__builtin_amdgcn_ds_bpermute(addr, (int)w.y);
-  return __builtin_bit_cast(double, r);
-}
-
-// the value of lane (lane ^ M).  Inside a row of 16 lanes the masks 1, 2, 3, 7, 8 and 15 are DPP moves on the VALU
-// (quad_perm [1,0,3,2], [2,3,0,1], [3,2,1,0], row_half_mirror, row_ror:8, row_mirror); the others go through the LDS
-// crossbar (ds_bpermute_b32, no LDS storage).  Every lane is active wherever this is called.
-template <int M>
-__device__ __forceinline__ double ef_xor_lane(double v, int lane) {
-  constexpr int ctrl = M == 1 ? 0xB1 : M == 2 ? 0x4E : M == 3 ? 0x1B : M == 7 ? 0x141 : M == 8 ? 0x128 : M == 15 ? 0x140 : -1;
-  if constexpr (ctrl >= 0) {
-    const u32x2 w = __builtin_bit_cast(u32x2, v);
-    u32x2 r;
-    r.x = (unsigned)__builtin_amdgcn_update_dpp(0, (int)w.x, ctrl, 0xF, 0xF, true);
-    r.y = (unsigned)__builtin_amdgcn_update_dpp(0, (int)w.y, ctrl, 0xF, 0xF, true);
-    return __builtin_bit_cast(double, r);
-  } else {
-    return ef_permute(v, (lane ^ M) << 2);
-  }
-}
-
-// sums over the wave in a fixed order (xor butterfly: every lane adds the same pairs, so every lane holds the same
-// bits), NB independent sums at a time
-template <int NB, int OFF>
-__device__ __forceinline__ void ef_wave_sum_from(double (&v)[NB], int lane) {
-  if constexpr (OFF < kWave) {
-    double o[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) o[b] = ef_xor_lane<OFF>(v[b], lane);
-#pragma unroll
-    for (int b = 0; b < NB; ++b) v[b] += o[b];
-    ef_wave_sum_from<NB, 2 * OFF>(v, lane);
-  }
-}
-template <int NB>
-__device__ __forceinline__ void ef_wave_sum(double (&v)[NB], int lane) {
-  ef_wave_sum_from<NB, 1>(v, lane);
-}
-
-// Ascending bitonic sort of the 64 V keys of a wave; the key of lane l, slot s has index i = l V + s.  The merge of
-// size k starts with the mirror exchange i <-> i ^ (k - 1) and goes on with i <-> i ^ j, j = k / 4 .. 1, so every
-// compare-exchange puts the minimum at the lower index (no descending runs).  Exchanges inside a lane (j < V) are
-// min / max pairs; an exchange between lanes fetches the partner's key and keeps one of the two.  Keys must not be
-// NaN (the caller replaces NaN by +Inf).
-template <int V>
-constexpr int ef_log2v() { return V == 1 ? 0 : (V == 2 ? 1 : (V == 4 ? 2 : 3)); }
-
-// one compare-exchange i <-> i ^ (1 << JB) of every key of NB independent key sets (every index a template
-// constant: the keys stay in registers; the sets' exchanges are issued together, so the NB dependent chains overlap)
-template <int NB, int V, int JB>
-__device__ __forceinline__ void ef_exchange(double (&key)[NB][V], int lane) {
-  constexpr int LV = ef_log2v<V>();
-  if constexpr (JB < LV) {
-    constexpr int j = 1 << JB;
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-      for (int s = 0; s < V; ++s) {
-        if ((s & j) == 0) {
-          const double lo = __builtin_fmin(key[b][s], key[b][s | j]), hi = __builtin_fmax(key[b][s], key[b][s | j]);
-          key[b][s] = lo;
-          key[b][s | j] = hi;
-        }
-      }
-  } else {
-    constexpr int jl = 1 << (JB - LV);
-    const bool upper = (lane & jl) != 0;
-    double o[NB][V];
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-      for (int s = 0; s < V; ++s) o[b][s] = ef_xor_lane<jl>(key[b][s], lane);
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-      for (int s = 0; s < V; ++s) key[b][s] = ((o[b][s] < key[b][s]) != upper) ? o[b][s] : key[b][s];
-  }
-}
-
-template <int NB, int V, int JB>
-__device__ __forceinline__ void ef_exchanges_down(double (&key)[NB][V], int lane) {
-  if constexpr (JB >= 0) {
-    ef_exchange<NB, V, JB>(key, lane);
-    ef_exchanges_down<NB, V, JB - 1>(key, lane);
-  }
-}
-
-// the merge of size 1 << KB: the mirror exchange, then i <-> i ^ j for j = (1 << KB) / 4 .. 1
-template <int NB, int V, int KB>
-__device__ __forceinline__ void ef_merge(double (&key)[NB][V], int lane) {
-  constexpr int LV = ef_log2v<V>();
-  if constexpr (KB <= LV) {
-    constexpr int m = (1 << KB) - 1;
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-      for (int s = 0; s < V; ++s) {
-        if (s < (s ^ m)) {
-          const double lo = __builtin_fmin(key[b][s], key[b][s ^ m]), hi = __builtin_fmax(key[b][s], key[b][s ^ m]);
-          key[b][s] = lo;
-          key[b][s ^ m] = hi;
-        }
-      }
-  } else {
-    constexpr int lm = (1 << (KB - LV)) - 1;  // partner lane = lane ^ lm, partner slot = V - 1 - s
-    const bool upper = (lane & (1 << (KB - LV - 1))) != 0;
-    double o[NB][V];
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-      for (int s = 0; s < V; ++s) o[b][s] = ef_xor_lane<lm>(key[b][V - 1 - s], lane);
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-      for (int s = 0; s < V; ++s) key[b][s] = ((o[b][s] < key[b][s]) != upper) ? o[b][s] : key[b][s];
-  }
-  ef_exchanges_down<NB, V, KB - 2>(key, lane);
-}
-
-template <int NB, int V, int KB>
-__device__ __forceinline__ void ef_merges_up(double (&key)[NB][V], int lane) {
-  if constexpr (KB <= ef_log2v<V>() + 6) {
-    ef_merge<NB, V, KB>(key, lane);
-    ef_merges_up<NB, V, KB + 1>(key, lane);
-  }
-}
-
-template <int NB, int V>
-__device__ __forceinline__ void ef_sort(double (&key)[NB][V], int lane) {
-  ef_merges_up<NB, V, 1>(key, lane);
-}
 
 // ---------------------------------------------------------------------------------------------
 // effect_bands_kernel
@@ -182,28 +44,6 @@ struct EfArgs {
   double dt, drop;
   QuantileRank qr[INSITE_EFFECT_MAX_QUANTILES];  // per quantile: i and g of the header's formula
 };
-
-// the sorted key of index i (wave-uniform), in every lane
-template <int V>
-__device__ __forceinline__ double ef_rank_value(const double (&key)[V], int i) {
-  constexpr int LV = ef_log2v<V>();
-  // the slot by a select tree over the bits of i (a chain of slot == s selects, and with V = 2 the one select
-  // between the two keys, is turned into an indexed scratch array: V = 2 selects between the two lane values instead)
-  if constexpr (V == 2) {
-    const double x0 = readlane_f64(key[0], i >> 1), x1 = readlane_f64(key[1], i >> 1);
-    return (i & 1) ? x1 : x0;
-  }
-  double x[V];
-#pragma unroll
-  for (int s = 0; s < V; ++s) x[s] = key[s];
-#pragma unroll
-  for (int b = 0; b < LV; ++b) {
-    const bool odd = ((i >> b) & 1) != 0;
-#pragma unroll
-    for (int s = 0; s < (V >> (b + 1)); ++s) x[s] = odd ? x[2 * s + 1] : x[2 * s];
-  }
-  return readlane_f64(x[0], i >> LV);
-}
 
 // NSER: 1 (plan A only) or 3 series.  The three series of a step are sorted together where the registers allow it
 // (V <= 4: three independent chains of dependent exchanges in flight); V = 8 sorts them one after the other.

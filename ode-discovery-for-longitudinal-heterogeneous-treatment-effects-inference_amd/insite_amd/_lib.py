@@ -35,6 +35,9 @@ EFFECT_ABI_VERSION, EFFECT_MAX_REPLICATES, EFFECT_MAX_QUANTILES = 1, 512, 16   #
 # include/insite_cohort.h
 COHORT_ABI_VERSION, COHORT_MAX_REPLICATES, COHORT_MAX_GROUPS, COHORT_MAX_QUANTILES = 1, 4096, 64, 16
 COHORT_WEIGHT_NONE, COHORT_WEIGHT_POISSON = 0, 1
+# include/insite_regimen.h
+REGIMEN_ABI_VERSION, REGIMEN_MAX_REPLICATES, REGIMEN_MAX_QUANTILES, REGIMEN_MAX_PLANS = 1, 512, 16, 16
+REGIMEN_MINIMIZE, REGIMEN_MAXIMIZE = 1, -1
 METHOD_EULER, METHOD_RK4 = 0, 1
 LAYOUT_PATIENT_MAJOR, LAYOUT_TIME_MAJOR, LAYOUT_TIME_MAJOR_BITS, LAYOUT_PATIENT_MAJOR_BITS = 0, 1, 2, 3
 MAX_TERMS, MAX_STATICS, MAX_ARMS, MAX_STATE_DEGREE = 9, 3, 4, 1
@@ -129,6 +132,14 @@ COHORT_EXPORTS = (
     "insite_cohort_effect_sums_f64",
     "insite_cohort_effect_finalize_f64",
     "insite_cohort_effect_f64",
+)
+
+# the extension header include/insite_regimen.h (same shared library, its own ABI version; a list of its own:
+# the six lists above are pinned by tests)
+REGIMEN_EXPORTS = (
+    "insite_regimen_abi_version",
+    "insite_regimen_workspace_bytes",
+    "insite_regimen_choice_f64",
 )
 
 
@@ -282,6 +293,12 @@ _SIGNATURES = {
                                           _c_i32, _c_f64, _c_i32, _c_i32, _c_f64, _c_i32, _vp, _c_i32, _c_i32,
                                           ctypes.c_uint32, _c_i64, _vp, _c_i64, _vp, _vp, _c_i32, _vp, _c_i64, _vp,
                                           _c_size, _vp]),
+    # insite_regimen.h
+    "insite_regimen_abi_version": (_c_i32, []),
+    "insite_regimen_workspace_bytes": (_c_size, [_c_i64, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32]),
+    "insite_regimen_choice_f64": (_c_i32, [_vp, _vp, _vp, _c_i32, _c_i64, _c_i64, _vp, _c_i64, _vp, _c_i32, _vp, _vp,
+                                           _c_i32, _c_i64, _c_i32, _c_i32, _c_i32, _c_f64, _c_i32, _c_i32, _c_f64,
+                                           _c_i32, _vp, _c_i32, _vp, _vp, _vp, _c_i64, _vp, _c_size, _vp]),
 }
 
 # (getter, the version these bindings were written for, the label of the mismatch message)
@@ -292,6 +309,7 @@ _ABI_VERSIONS = (
     ("insite_bootstrap_abi_version", BOOTSTRAP_ABI_VERSION, "bootstrap "),
     ("insite_effect_abi_version", EFFECT_ABI_VERSION, "effect "),
     ("insite_cohort_abi_version", COHORT_ABI_VERSION, "cohort "),
+    ("insite_regimen_abi_version", REGIMEN_ABI_VERSION, "regimen "),
 )
 
 

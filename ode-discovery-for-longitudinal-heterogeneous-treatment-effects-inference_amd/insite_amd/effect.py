@@ -78,3 +78,46 @@ def from_cohort(out: torch.Tensor, wsum: torch.Tensor, q, shift: float = 0.0, sc
     res[:min(S, 2), loc] = (o[:min(S, 2), loc] - shift) / scale
     return CohortEffectResult(point=res[:, 0], mean=res[:, 1], std=res[:, 2], quantiles=res[:, 3:], weight_sum=wsum,
                               q=tuple(float(v) for v in q), series=SERIES[:S])
+
+
+REGIMEN_SERIES = ("value", "regret")
+
+
+@dataclasses.dataclass
+class RegimenChoiceResult:
+    """The choice among K treatment plans of ``ops.regimen_choice`` (include/insite_regimen.h).
+    ``choice`` int32 [N]: the point model's best plan (-1: the point model has a NaN objective); ``win`` [N, K]: the
+    share of the replicates 1..R-1 in which plan j is the best (a row sums to 1 minus the share of replicates that
+    abstain).  ``series``: ("value", "regret").  ``point``, ``mean``, ``std`` [2, N, K]: per plan the objective and the
+    regret against the replicate's own best plan, as the point model's value and the mean / standard deviation (n - 1
+    divisor) over the replicates 1..R-1; ``quantiles`` [2, Q, N, K] in the order of ``q``.  ``result["regret"]`` gives
+    one series as a dict."""
+    choice: torch.Tensor
+    win: torch.Tensor
+    point: torch.Tensor
+    mean: torch.Tensor
+    std: torch.Tensor
+    quantiles: torch.Tensor
+    q: tuple
+    series: tuple = REGIMEN_SERIES
+
+    def __getitem__(self, name: str) -> dict:
+        i = self.series.index(name)
+        return {"point": self.point[i], "mean": self.mean[i], "std": self.std[i], "quantiles": self.quantiles[i]}
+
+
+def from_regimen(choice: torch.Tensor, win: torch.Tensor, out: torch.Tensor, q, shift=0.0,
+                 scale: float = 1.0) -> RegimenChoiceResult:
+    """``ops.regimen_choice``'s (choice, win, out [N, K, 2, 3 + Q]) as a ``RegimenChoiceResult`` in the scale
+    (x - shift) / scale: the locations of the value series (point, mean, quantiles) are shifted and divided, its
+    standard deviation and every statistic of the regret (a difference: the shift cancels) are divided only.
+    ``shift``: a number or a tensor [N] (the shift of a weighted sum is the row's weight total times the mean)."""
+    if out.dim() != 4 or out.size(2) != 2 or out.size(3) != 3 + len(q):
+        raise ValueError("out must be [N, K, 2, 3 + Q]")
+    o = out.permute(2, 3, 0, 1)                     # [2, 3 + Q, N, K]
+    res = o / scale
+    loc = [0, 1] + list(range(3, o.size(1)))        # point, mean and quantiles
+    sh = shift[:, None] if isinstance(shift, torch.Tensor) else shift
+    res[0, loc] = (o[0, loc] - sh) / scale
+    return RegimenChoiceResult(choice=choice, win=win, point=res[:, 0], mean=res[:, 1], std=res[:, 2],
+                               quantiles=res[:, 3:], q=tuple(float(v) for v in q))

@@ -985,6 +985,113 @@ def plan_effect_bands(y0, u, arm_a, arm_b, coef, lib, dt, quantiles, method="eul
     return Plan(name, args, dev, out, keep)
 
 
+def _prep_regimen_choice(y0, u, plans, coef, lib, dt, quantiles, weights, cost, maximize, method, substeps, drop_below,
+                         T, out, workspace):
+    """Validate the inputs of the regimen choice and pack the C arguments (insite_regimen.h)."""
+    L = _lib.load()
+    _dev("y0", y0, torch.float64, 1)
+    N = y0.numel()
+    if not isinstance(plans, torch.Tensor) or not plans.is_cuda:
+        _dev("plans", plans, torch.int8)
+    if plans.dim() not in (2, 3):
+        raise ValueError("plans must be int8 [K, T] (shared by the rows) or [K, N, >=T]")
+    _dev("plans", plans, torch.int8, plans.dim())
+    K = plans.size(0)
+    if not 1 <= K <= _lib.REGIMEN_MAX_PLANS:
+        raise ValueError(f"between 1 and {_lib.REGIMEN_MAX_PLANS} plans expected, got {K}")
+    T = plans.size(-1) if T is None else int(T)
+    if T < 1 or plans.size(-1) < T:
+        raise ValueError("T must be >= 1 and the plans must hold at least T steps")
+    if plans.dim() == 2:
+        ld_plan, plan_stride = 0, (plans.stride(0) if K > 1 else T)
+    else:
+        if plans.size(1) != N:
+            raise ValueError("plans must be int8 [K, T] (shared by the rows) or [K, N, >=T]")
+        ld_plan = plans.stride(1) if N > 1 else T
+        plan_stride = plans.stride(0) if K > 1 and N > 0 else max(N, 1) * ld_plan
+        if ld_plan < T or plan_stride < N * ld_plan:
+            raise ValueError("plans: overlapping rows or plans")
+    if plan_stride < T:
+        raise ValueError("plans: overlapping plans")
+    if not isinstance(weights, torch.Tensor) or not weights.is_cuda or weights.dim() not in (1, 2):
+        _dev("weights", weights, torch.float64)
+        raise ValueError("weights must be f64 [T] (shared by the rows) or [N, >=T]")
+    _dev("weights", weights, torch.float64, weights.dim())
+    if weights.size(-1) < T or (weights.dim() == 2 and weights.size(0) != N):
+        raise ValueError("weights must be f64 [T] (shared by the rows) or [N, >=T]")
+    ld_w = 0 if weights.dim() == 1 else (weights.stride(0) if N > 1 else T)
+    if cost is not None:
+        _dev("cost", cost, torch.float64, 1)
+        if cost.numel() != K or not cost.is_contiguous():
+            raise ValueError("cost must be a contiguous f64 [K] tensor")
+    if lib.n_statics:
+        _dev("u", u, torch.float64, 2)
+        if u.size(0) != N or u.size(1) != lib.n_statics or u.stride(0) != lib.n_statics:
+            raise ValueError("u must be a contiguous [N, n_statics] tensor")
+    _dev("coef", coef, torch.float64, 3)
+    if not coef.is_contiguous() or coef.size(-1) != lib.n_terms:
+        raise ValueError("coef must be a contiguous [R, n_arms, F] tensor")
+    R, A, F = coef.size(0), coef.size(1), lib.n_terms
+    if not 1 <= A <= _lib.MAX_ARMS:
+        raise ValueError(f"n_arms must be in [1, {_lib.MAX_ARMS}]")
+    if not 2 <= R <= _lib.REGIMEN_MAX_REPLICATES:
+        raise ValueError(f"n_replicates must be in [2, {_lib.REGIMEN_MAX_REPLICATES}] (replicate 0 is the point model)")
+    q = _quantiles(quantiles, _lib.REGIMEN_MAX_QUANTILES)
+    m, sub = _method(method, substeps)
+    dev = y0.device
+    NS = 3 + q.size
+    shape = (N, K, 2, NS)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=dev)
+        ld_out = K * 2 * NS
+    else:
+        _dev("out", out, torch.float64, 4)
+        ld_out = out.stride(0) if N > 1 else K * 2 * NS
+        if (tuple(out.shape) != shape or ld_out < K * 2 * NS
+                or (N > 0 and (out.stride(3) != 1 or out.stride(2) != NS or (K > 1 and out.stride(1) != 2 * NS)))):
+            raise ValueError(f"out must be {shape}, every row's [K, 2, 3 + Q] block dense (rows may be padded)")
+    choice = torch.empty(N, dtype=torch.int32, device=dev)
+    win = torch.empty((N, K), dtype=torch.float64, device=dev)
+    ws_bytes = L.insite_regimen_workspace_bytes(N, T, A, F, R, q.size, K)
+    ws = _ws(workspace, dev, "scratch").get(ws_bytes, dev) if ws_bytes else None
+    tab = lib.ctypes_table()
+    args = (_p(y0), _p(u) if lib.n_statics else ctypes.c_void_p(0), _p(plans), K, plan_stride, ld_plan, _p(weights),
+            ld_w, _p(cost), _lib.REGIMEN_MAXIMIZE if maximize else _lib.REGIMEN_MINIMIZE, _p(coef),
+            tab.ctypes.data_as(ctypes.c_void_p), F, N, T, lib.n_statics, A, float(dt), m, sub, float(drop_below), R,
+            q.ctypes.data_as(ctypes.c_void_p), q.size, _p(choice), _p(win), _p(out), ld_out, _p(ws),
+            ws.numel() if ws is not None else 0)
+    return ("insite_regimen_choice_f64", args, dev, (choice, win, out),
+            (y0, u, plans, weights, cost, coef, tab, q, ws, choice, win, out))
+
+
+def regimen_choice(y0: torch.Tensor, u: torch.Tensor, plans: torch.Tensor, coef: torch.Tensor, lib: PolyLibrary,
+                   dt: float, quantiles, weights: torch.Tensor, cost: torch.Tensor | None = None,
+                   maximize: bool = False, method: str = "euler5", substeps: int | None = None,
+                   drop_below: float = 1e-3, T: int | None = None, out: torch.Tensor | None = None,
+                   workspace: Workspace | None = None):
+    """Which of K treatment plans is best for every row, over a bootstrap ensemble (insite_regimen_choice_f64,
+    DESIGN.md §9j).
+
+    y0 [N] f64, u [N, U] f64, plans int8 [K, T] (shared by the rows) or [K, N, >=T] per-step arms, coef [R, A, F]:
+    replicate 0 the point model, replicates 1..R-1 the resamples (``sindy_bootstrap``); weights f64 [T] or [N, >=T],
+    cost f64 [K] or None.  The objective of plan j under replicate r is J = cost[j] + sum_k w[p, k] y_j[r, p, k]; the
+    best plan is taken inside each replicate (minimum, or maximum with ``maximize``; ties to the lower index; a
+    replicate with a NaN objective abstains).  Returns (choice int32 [N]: the point model's plan, -1 if it abstains;
+    win f64 [N, K]: every plan's share of the votes of the replicates 1..R-1; out f64 [N, K, 2, 3 + Q]: per plan the
+    objective and the regret against the replicate's best plan, each as point value, mean, standard deviation (ddof
+    1) and the ``quantiles`` over the replicates 1..R-1).  The replicate objectives never exist in memory."""
+    return _run(_prep_regimen_choice(y0, u, plans, coef, lib, dt, quantiles, weights, cost, maximize, method, substeps,
+                                     drop_below, T, out, workspace))
+
+
+def plan_regimen_choice(y0, u, plans, coef, lib, dt, quantiles, weights, cost=None, maximize=False, method="euler5",
+                        substeps=None, drop_below=1e-3, T=None, out=None, workspace=None) -> Plan:
+    """``regimen_choice`` as a prepared launch; ``plan.out`` = (choice, win, out)."""
+    name, args, dev, outs, keep = _prep_regimen_choice(y0, u, plans, coef, lib, dt, quantiles, weights, cost, maximize,
+                                                       method, substeps, drop_below, T, out, workspace)
+    return Plan(name, args, dev, outs, keep)
+
+
 COHORT_WEIGHTINGS = {"none": _lib.COHORT_WEIGHT_NONE, "poisson": _lib.COHORT_WEIGHT_POISSON}
 
 

@@ -571,6 +571,58 @@ class SINDY:
                                method=self.integrator, drop_below=0.0, T=arm_a.size(1))
         return effect.from_bands(out, quantiles, shift=mean, scale=std)
 
+    # ------------------------------------------------------------------ regimen choice
+    def _objective_weights(self, dataset, objective):
+        """The step weights of ``choose_plan``: f64 [T] or [N, T] on the host."""
+        ae = np.asarray(dataset.data["active_entries"][..., 0], dtype=np.float64)
+        N, T = ae.shape
+        if isinstance(objective, str):
+            if objective == "mean":
+                tot = ae.sum(axis=1, keepdims=True)
+                return np.divide(ae, tot, out=np.zeros_like(ae), where=tot > 0)
+            if objective == "terminal":
+                w = np.zeros_like(ae)
+                has = (ae > 0).any(axis=1)
+                last = T - 1 - np.argmax(ae[:, ::-1] > 0, axis=1)
+                w[np.nonzero(has)[0], last[has]] = 1.0
+                return w
+            raise ValueError("objective must be 'mean', 'terminal', an array [T] or an array [N, T]")
+        w = objective.detach().cpu().numpy() if isinstance(objective, torch.Tensor) else np.asarray(objective)
+        if w.shape not in ((T,), (N, T)):
+            raise ValueError(f"objective must be 'mean', 'terminal', an array [{T}] or an array [{N}, {T}]")
+        return w.astype(np.float64)
+
+    def choose_plan(self, dataset, plans, objective="mean", costs=None, maximize=False,
+                    quantiles=(0.025, 0.5, 0.975)):
+        """Which of the candidate ``plans`` is best for every row of ``dataset``, and how sure the bootstrap ensemble
+        is of it.  ``plans``: a list of 1..16 plans, each as ``treatment_effect`` takes them (None, an int, an int
+        array [N, T] or a one-hot array [N, T, A]).  The objective of a plan is cost + sum_k w[p, k] y[p, k] over its
+        predicted trajectory (standardised like ``get_predictions``): ``objective`` "mean" (the mean over the row's
+        active entries), "terminal" (the row's last active step), or weights [T] / [N, T]; ``costs``: one number per
+        plan in the same units; the smallest objective wins (the largest with ``maximize``).  The best plan is taken
+        inside each bootstrap replicate, so ``win`` is the share of replicates in which a plan is the best -- not
+        recoverable from per-plan or pairwise bands.  Returns an ``effect.RegimenChoiceResult``: ``choice`` (the
+        point model's plan), ``win`` [N, K] and per plan the series "value" and "regret" (against the replicate's own
+        best plan; divided by the output's standard deviation only).  One launch of ``ops.regimen_choice``."""
+        coef = self._effect_coef("choose_plan")
+        if not isinstance(plans, (list, tuple)) or not 1 <= len(plans) <= _lib.REGIMEN_MAX_PLANS:
+            raise ValueError(f"choose_plan: plans must be a list of 1 to {_lib.REGIMEN_MAX_PLANS} plans")
+        K = len(plans)
+        if costs is not None and np.asarray(costs, dtype=np.float64).shape != (K,):
+            raise ValueError(f"choose_plan: costs must hold one number per plan ({K})")
+        prev, stat, std, mean = self._unscaled_inputs(dataset)
+        arms = torch.stack([self._plan_arms(dataset, pl, f"plans[{j}]") for j, pl in enumerate(plans)]).contiguous()
+        w = torch.as_tensor(np.ascontiguousarray(self._objective_weights(dataset, objective)), device=self.device)
+        cost = None
+        if costs is not None:
+            cost = torch.as_tensor(np.asarray(costs, dtype=np.float64) * std, device=self.device)
+        choice, win, out = ops.regimen_choice(prev[:, 0].contiguous(), stat, arms, coef, self.library, self.dt,
+                                              quantiles, w, cost=cost, maximize=maximize, method=self.integrator,
+                                              drop_below=0.0, T=arms.size(2))
+        shift = mean * w.sum(dim=-1)                # a number (shared weights) or [N]
+        return effect.from_regimen(choice, win, out, quantiles, shift=shift if w.dim() == 2 else float(shift),
+                                   scale=std)
+
     # ------------------------------------------------------------------ cohort averages (DESIGN.md §9i)
     def _groups(self, groups, N):
         """``groups`` None (one group) or int ids [N] (negative: the row is excluded) -> (int32 device tensor or None,
