@@ -1,13 +1,16 @@
 // insite_affine.h — the one definition of what every translation unit of the affine libraries (state exponent
 // <= INSITE_MAX_STATE_DEGREE) shares: the exponent-table checks and their packed codes, the Gram entry list, the
-// quantile ranks, the bootstrap weight stream (Threefry-2x32-20 + the Poisson(1) inverse CDF) and the interval map of
-// the rollout.  Two contracts rest on there being one copy: DESIGN.md §9i (the cohort kernel's weight of (seed,
-// replicate, global patient) is §9g's, bit for bit) and §9h (the effect and cohort trajectories are rollout's).
+// quantile ranks and interpolation, the bootstrap weight stream (Threefry-2x32-20 + the Poisson(1) inverse CDF), the
+// interval map of the rollout and, for the three consumers of the bootstrap ensemble, the
+// replicate fold with its keep-NaN rule and the host entry points' common checks and launch plan.  Two contracts rest
+// on there being one copy: DESIGN.md §9i (the cohort kernel's weight of (seed, replicate, global patient) is §9g's,
+// bit for bit) and §9h (the effect and cohort trajectories are rollout's).
 // insite_common.h's convention: an anonymous namespace, each translation unit gets its own internal copy.
 #pragma once
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
 
 #include "insite_common.h"
 
@@ -118,6 +121,11 @@ inline QuantileRank quantile_rank(double q, int n) {
   return QuantileRank{i, pos - (double)i};
 }
 
+// include/insite_effect.h's formula between the sorted keys lo = s[i] and hi = s[min(i + 1, n - 1)]
+__device__ __forceinline__ double quantile_interp(double lo, double hi, double g) {
+  return (g == 0.0 || lo == hi) ? lo : lo + g * (hi - lo);
+}
+
 // ---------------------------------------------------------------------------------------------
 // weights: Threefry-2x32-20 (Salmon et al., SC'11; pinned by the Random123 known-answer vectors) and the Poisson(1)
 // inverse CDF
@@ -220,6 +228,106 @@ __device__ __forceinline__ double readlane_f64(double v, int src) {
   r.x = (unsigned)__builtin_amdgcn_readlane((int)w.x, src);
   r.y = (unsigned)__builtin_amdgcn_readlane((int)w.y, src);
   return __builtin_bit_cast(double, r);
+}
+
+// ---------------------------------------------------------------------------------------------
+// the bootstrap ensemble (insite_effect.hip, insite_cohort.hip, insite_regimen.hip): replicate fold and maps
+// ---------------------------------------------------------------------------------------------
+// One replicate's RHS of every arm, f_a(y) = al[a] + be[a] y, folded over the library's terms in ascending order.
+// coef(a, j): the replicate's coefficient of arm a < n_arms, term j; mono(j): the u-monomial of term j.  A dropped
+// term (|c| <= drop) adds 0 and a NaN coefficient is kept (insite_effect.h); insite_hip.hip's affine_rates_regs
+// drops it.
+template <int NARM, class Coef, class Mono>
+__device__ __forceinline__ void replicate_fold(const AffineLib& lib, int n_arms, double drop, Coef coef, Mono mono,
+                                               double (&al)[NARM], double (&be)[NARM]) {
+#pragma unroll
+  for (int a = 0; a < NARM; ++a) al[a] = be[a] = 0.0;
+#pragma unroll
+  for (int j = 0; j < INSITE_MAX_TERMS; ++j) {
+    if (j < lib.F) {
+      const double m = mono(j);
+      const bool lin = (lib.ucode[j] >> 24) != 0;
+#pragma unroll
+      for (int a = 0; a < NARM; ++a) {
+        if (a < n_arms) {
+          const double c = coef(a, j);
+          const double v = (fabs(c) > drop || c != c) ? c * m : 0.0;
+          if (lin) be[a] += v;
+          else al[a] += v;
+        }
+      }
+    }
+  }
+}
+
+// The prologue of a wave that holds the ensemble in registers (lane l, slot s = replicate s 64 + l; a slot past R
+// reads replicate 0 and is never used): the row's statics u_row, then per slot the fold and the interval map (PA, PB)
+// of every arm.  coef: [R][n_arms][F].
+template <int V, int NARM>
+__device__ __forceinline__ void ensemble_maps(const AffineLib& lib, const double* coef, const double* u_row, int R,
+                                              int n_arms, double drop, int method, int substeps, double h, int lane,
+                                              double (&PA)[V][NARM], double (&PB)[V][NARM]) {
+  double uu[INSITE_MAX_STATICS];
+#pragma unroll
+  for (int t = 0; t < INSITE_MAX_STATICS; ++t) uu[t] = t < lib.U ? u_row[t] : 0.0;
+#pragma unroll
+  for (int s = 0; s < V; ++s) {
+    const int r = s * kWave + lane;
+    const double* cb = coef + (int64_t)(r < R ? r : 0) * n_arms * lib.F;
+    double al[NARM], be[NARM];
+    replicate_fold<NARM>(
+        lib, n_arms, drop, [&](int a, int j) { return cb[a * lib.F + j]; },
+        [&](int j) { return monomial_code(lib.ucode[j] & 0xffffff, uu); }, al, be);
+#pragma unroll
+    for (int a = 0; a < NARM; ++a) interval_map(method, substeps, h, al[a], be[a], PA[s][a], PB[s][a]);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// the bootstrap ensemble: what the three host entry points share
+// ---------------------------------------------------------------------------------------------
+inline bool ensemble_shape_ok(int64_t n_rows, int32_t T, int32_t n_arms, int32_t substeps, double dt,
+                              int32_t n_replicates) {
+  return n_rows >= 0 && T >= 1 && n_arms >= 1 && n_arms <= INSITE_MAX_ARMS && substeps >= 1 && dt >= 0.0 &&
+         n_replicates >= 2;  // (a NaN dt fails its comparison)
+}
+
+// after the caller's INVALID_ARG checks, in the order the headers document: the method, the exponent table (packed
+// into lib), the replicate cap
+inline int32_t ensemble_lib(int32_t method, const int8_t* exps, int32_t n_terms, int32_t n_statics,
+                            int32_t n_replicates, int32_t max_replicates, AffineLib* lib) {
+  if (method != INSITE_METHOD_EULER && method != INSITE_METHOD_RK4) return INSITE_E_UNSUPPORTED;
+  const int32_t st = build_affine_lib(exps, n_terms, n_statics, lib);
+  if (st != INSITE_OK) return st;
+  return n_replicates > max_replicates ? INSITE_E_UNSUPPORTED : INSITE_OK;
+}
+
+// wave = row: the rows one block walks, so that a launch has at most 2^20 blocks
+inline int64_t rows_per_block(int64_t n_rows) {
+  const int64_t blocks = n_rows < (1 << 20) ? n_rows : (1 << 20);
+  return (n_rows + blocks - 1) / blocks;
+}
+
+// the register slots of a kernel instantiation: V = R_pad / 64 replicates per lane and NARM arms, handed to f as
+// integral constants
+inline int replicate_slots(int n_replicates) {
+  return n_replicates <= 64 ? 1 : (n_replicates <= 128 ? 2 : (n_replicates <= 256 ? 4 : 8));
+}
+template <class F>
+void with_arm_slots(int n_arms, F f) {
+  if (n_arms <= 1) f(std::integral_constant<int, 1>());
+  else if (n_arms <= 2) f(std::integral_constant<int, 2>());
+  else f(std::integral_constant<int, 4>());
+}
+template <class F>
+void with_slots(int n_replicates, int n_arms, F f) {
+  with_arm_slots(n_arms, [&](auto narm) {
+    const int v = replicate_slots(n_replicates);
+    if (v == 1) f(std::integral_constant<int, 1>(), narm);
+    else if (v == 2) f(std::integral_constant<int, 2>(), narm);
+    else if (v == 4) f(std::integral_constant<int, 4>(), narm);
+    else f(std::integral_constant<int, 8>(), narm);
+  });
 }
 
 }  // namespace

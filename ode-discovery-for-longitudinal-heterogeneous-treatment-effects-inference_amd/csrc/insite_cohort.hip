@@ -6,7 +6,8 @@
 //                          tile of 16 or 32 steps and a contiguous chunk of patients.  It reads 64 group ids at a time,
 //                          takes the ballot of `group == g` and visits the set bits, so the group test is
 //                          wave-uniform.  Per visited patient (its y0, u and arms loaded one patient ahead): the
-//                          affine fold and the interval maps of effect_bands_kernel, the lane's Poisson weight (one
+//                          affine fold (insite_affine.h's replicate_fold, the one effect_bands_kernel uses, with the
+//                          coefficients from LDS) and the interval maps, the lane's Poisson weight (one
 //                          Threefry block per pair of global patient indices), the arms of 64 steps as ballot masks
 //                          (the step's arm is a scalar bit test), then per plan and step one FMA per arm and a
 //                          select; the steps of the block's tile add w y to lane-private register accumulators, the
@@ -15,7 +16,8 @@
 //                          to its workspace slot.
 //   cohort_reduce_kernel   thread = one element of sums / wsum: the chunks' partials in chunk order.
 //   cohort_finalize_kernel block = (group, step): the means of the 1 or 3 series, per series the fixed-order mean and
-//                          two-pass deviation and a bitonic sort of the R_pad keys in LDS.
+//                          two-pass deviation and a bitonic sort of the R_pad keys in LDS; the quantile interpolation
+//                          is insite_affine.h's quantile_interp, as are the host's common checks and NARM choice.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -233,26 +235,13 @@ __global__ void __launch_bounds__(kWave) cohort_sums_kernel(CoArgs ca, AffineLib
     wacc += w;
     // ---- prologue: the interval maps of the lane's replicate --------------------------------------------------
     // A patient's monomials are wave-uniform, so lane j computes term j once (the trip counts differ between lanes,
-    // not between the terms' turns) and the fold reads it back as a scalar.
+    // not between the terms' turns) and insite_affine.h's fold reads it back as a scalar, the coefficients from LDS
+    // (all NARM arms: those past n_arms hold zeros and no step selects them).
     const double m_l = monomial_code(code_l, row.uu);
     double al[NARM], be[NARM];
-#pragma unroll
-    for (int a = 0; a < NARM; ++a) al[a] = be[a] = 0.0;
-#pragma unroll
-    for (int j = 0; j < INSITE_MAX_TERMS; ++j) {
-      if (j < lib.F) {
-        const double m = readlane_f64(m_l, j);
-        const bool lin = (lib.ucode[j] >> 24) != 0;
-#pragma unroll
-        for (int a = 0; a < NARM; ++a) {  // (the arms past n_arms hold zeros and no step selects them)
-          const double c = cs[(a * lib.F + j) * kWave + lane];
-          // a dropped term adds 0; a NaN coefficient is kept (insite_effect.h)
-          const double v = (fabs(c) > ca.drop || c != c) ? c * m : 0.0;
-          if (lin) be[a] += v;
-          else al[a] += v;
-        }
-      }
-    }
+    replicate_fold<NARM>(
+        lib, NARM, ca.drop, [&](int a, int j) { return cs[(a * lib.F + j) * kWave + lane]; },
+        [&](int j) { return readlane_f64(m_l, j); }, al, be);
     // a row the replicate did not draw rolls the zero trajectory of the zero map: a select, so that its y0 and u
     // (NaN or not) reach nothing
     double PA[NARM], PB[NARM];
@@ -453,9 +442,7 @@ __global__ void __launch_bounds__(kCoFinBlock) cohort_finalize_kernel(CoFinArgs 
     }
     if (t < fa.Q) {
       const int i = (int)fa.qr[t].i;
-      const double gq = fa.qr[t].g;
-      const double lo = key[i], hi = key[i + 1 < n ? i + 1 : n - 1];
-      const double qv = (gq == 0.0 || lo == hi) ? lo : lo + gq * (hi - lo);
+      const double qv = quantile_interp(key[i], key[i + 1 < n ? i + 1 : n - 1], fa.qr[t].g);
       o[(3 + t) * fa.ldo] = any_nan ? nan : qv;
     }
   }
@@ -464,12 +451,7 @@ __global__ void __launch_bounds__(kCoFinBlock) cohort_finalize_kernel(CoFinArgs 
 // ---------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------
-int32_t co_check_shape(int64_t n_rows, int32_t T, int32_t n_arms, int32_t n_replicates, int32_t n_groups) {
-  if (n_rows < 0 || T < 1 || n_arms < 1 || n_arms > INSITE_MAX_ARMS || n_replicates < 2 || n_groups < 1 ||
-      n_groups > INSITE_COHORT_MAX_GROUPS)
-    return INSITE_E_INVALID_ARG;
-  return INSITE_OK;
-}
+bool co_groups_ok(int32_t n_groups) { return n_groups >= 1 && n_groups <= INSITE_COHORT_MAX_GROUPS; }
 
 struct CoSumsCall {
   CoArgs ca;
@@ -486,14 +468,13 @@ int32_t co_prepare_sums(const double* y0, const double* u, const int8_t* arm_a, 
                         double drop_below, int32_t n_replicates, const int32_t* group, int32_t n_groups,
                         int32_t weighting, uint32_t seed, int64_t patient_offset, double* sums, int64_t ld_sums,
                         double* wsum, void* workspace, size_t workspace_bytes, CoSumsCall* c) {
-  if (co_check_shape(n_rows, T, n_arms, n_replicates, n_groups) != INSITE_OK || substeps < 1 || !(dt >= 0.0) ||
+  if (!ensemble_shape_ok(n_rows, T, n_arms, substeps, dt, n_replicates) || !co_groups_ok(n_groups) ||
       ld_arm_a < (int64_t)T || (arm_b && ld_arm_b < (int64_t)T) || ld_sums < (int64_t)T || patient_offset < 0 ||
       (weighting != INSITE_COHORT_WEIGHT_NONE && weighting != INSITE_COHORT_WEIGHT_POISSON))
     return INSITE_E_INVALID_ARG;
-  if (method != INSITE_METHOD_EULER && method != INSITE_METHOD_RK4) return INSITE_E_UNSUPPORTED;
-  const int32_t st = build_affine_lib(exps, n_terms, n_statics, &c->lib);
+  const int32_t st =
+      ensemble_lib(method, exps, n_terms, n_statics, n_replicates, INSITE_COHORT_MAX_REPLICATES, &c->lib);
   if (st != INSITE_OK) return st;
-  if (n_replicates > INSITE_COHORT_MAX_REPLICATES) return INSITE_E_UNSUPPORTED;
   c->nser = arm_b ? 2 : 1;
   c->empty = n_rows == 0;
   if (c->empty) return INSITE_OK;
@@ -535,23 +516,18 @@ int32_t co_prepare_sums(const double* y0, const double* u, const int8_t* arm_a, 
 }
 
 template <int TT, int NARM>
-void co_launch_sums_ta(const CoSumsCall& c, dim3 grid, hipStream_t hs) {
+void co_launch_sums(const CoSumsCall& c, dim3 grid, hipStream_t hs) {
   if (c.nser == 2) cohort_sums_kernel<TT, NARM, 2><<<grid, kWave, 0, hs>>>(c.ca, c.lib);
   else cohort_sums_kernel<TT, NARM, 1><<<grid, kWave, 0, hs>>>(c.ca, c.lib);
-}
-
-template <int NARM>
-void co_launch_sums(const CoSumsCall& c, dim3 grid, hipStream_t hs) {
-  if (c.plan.tile == kCoTtShort) co_launch_sums_ta<kCoTtShort, NARM>(c, grid, hs);
-  else co_launch_sums_ta<kCoTtLong, NARM>(c, grid, hs);
 }
 
 int32_t co_run_sums(const CoSumsCall& c, double* sums, int64_t ld_sums, double* wsum, hipStream_t hs) {
   const CoArgs& ca = c.ca;
   const dim3 grid((unsigned)(c.plan.n_chunks * c.plan.n_rt * ca.G * c.plan.n_tt));
-  if (ca.A <= 1) co_launch_sums<1>(c, grid, hs);
-  else if (ca.A <= 2) co_launch_sums<2>(c, grid, hs);
-  else co_launch_sums<4>(c, grid, hs);
+  with_arm_slots(ca.A, [&](auto narm) {
+    if (c.plan.tile == kCoTtShort) co_launch_sums<kCoTtShort, narm()>(c, grid, hs);
+    else co_launch_sums<kCoTtLong, narm()>(c, grid, hs);
+  });
   const int64_t n_el = (int64_t)ca.G * c.plan.n_rt * kWave * ((int64_t)c.nser * ca.T + 1);
   cohort_reduce_kernel<<<(unsigned)((n_el + kCoRedBlock - 1) / kCoRedBlock), kCoRedBlock, 0, hs>>>(
       ca.partial, ca.wpart, c.plan.n_chunks, ca.G, c.plan.n_rt, c.nser, ca.T, ca.R, sums, ld_sums, wsum);
@@ -601,7 +577,8 @@ int32_t insite_cohort_abi_version(void) { return INSITE_COHORT_ABI_VERSION; }
 
 size_t insite_cohort_effect_workspace_bytes(int64_t n_rows, int32_t T, int32_t n_arms, int32_t n_terms,
                                             int32_t n_replicates, int32_t n_groups) {
-  if (co_check_shape(n_rows, T, n_arms, n_replicates, n_groups) != INSITE_OK || n_terms < 1 ||
+  // (no sub-steps and no dt here: 1 and 0 pass)
+  if (!ensemble_shape_ok(n_rows, T, n_arms, 1, 0.0, n_replicates) || !co_groups_ok(n_groups) || n_terms < 1 ||
       n_terms > INSITE_MAX_TERMS || n_replicates > INSITE_COHORT_MAX_REPLICATES || n_rows == 0)
     return 0;
   return co_plan(n_rows, T, n_replicates, n_groups).bytes;

@@ -4,15 +4,16 @@
 // Kernel:
 //   regimen_choice_kernel  wave = row.  Lane l holds V = R_pad / 64 replicates (replicate s 64 + l in slot s), as
 //                          effect_bands_kernel.  Prologue per row, once for all K plans: the affine fold and the
-//                          interval map (A_a, B_a) of every replicate and arm.  Phase 1, per plan: y = y0, J = cost[j];
-//                          the plan's arm bytes and the row's weights come in 16-step chunks (one load per lane, read
+//                          interval map (A_a, B_a) of every replicate and arm (insite_affine.h's ensemble_maps, as
+//                          the effect bands; the host checks and the choice of V and NARM are shared too).  Phase 1,
+//                          per plan: y = y0, J = cost[j]; the plan's arm bytes and the row's weights come in 16-step chunks (one load per lane, read
 //                          back by v_readlane: both are wave-uniform), the step's arm is a scalar branch, and a step is
 //                          two FMAs per replicate (y <- A y + B, J <- w y + J); the running strict minimum of s J and
 //                          its index stay in registers, and J goes to a lane-private LDS column [K - 1][R_pad] (a lane
 //                          reads only what it wrote: no barrier; the last plan's J stays in registers).  Then the
 //                          votes: ballot + popcount per plan over the valid slots.  Phase 2, per plan, last plan first:
 //                          J back from its column, the regret against the replicate's minimum, and the statistics of
-//                          both series by insite_wavestats.h's network (sorted together at V <= 4); the plan's
+//                          both series by insite_wavestats.h's ef_series_stats (sorted together at V <= 4); the plan's
 //                          [2, 3 + Q] block is staged in LDS and flushed as one contiguous segment of the row's block.
 #include <hip/hip_runtime.h>
 
@@ -30,7 +31,6 @@ namespace {
 constexpr int kRgTc = 16;                                    // steps per chunk of arm bytes and weights
 constexpr int kRgMaxStats = 3 + INSITE_REGIMEN_MAX_QUANTILES;
 constexpr int kRgStage = 40;                                 // doubles of the staging block: >= 2 kRgMaxStats
-constexpr int kRgMaxBlocks = 1 << 20;                        // blocks of one launch; past it a block walks a run of rows
 static_assert(2 * kRgMaxStats <= kRgStage && kRgStage <= kWave, "one plan's block is flushed by one wave at once");
 
 struct RgArgs {
@@ -81,72 +81,6 @@ __device__ __forceinline__ void rg_step(int aa, const double (&PA)[V][NARM], con
   }
 }
 
-// The statistics of NB series (insite_effect.h: point, shifted mean, two-pass standard deviation, quantiles, the NaN
-// rule) into st[b (3 + Q) + stat], written by lane 0.  The arithmetic and its order are effect_bands_kernel's.
-template <int NB, int V>
-__device__ __forceinline__ void rg_stats(const double (&v)[NB][V], const bool (&valid)[V], int lane, int n,
-                                         const RgArgs& ra, double* st) {
-  const double inf = std::numeric_limits<double>::infinity();
-  const double nan = std::numeric_limits<double>::quiet_NaN();
-  const int NS = 3 + ra.Q;
-  double key[NB][V];
-  bool any_nan[NB];
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    bool bad = false;
-#pragma unroll
-    for (int s = 0; s < V; ++s) {
-      const bool isn = v[b][s] != v[b][s];
-      bad = bad || (valid[s] && isn);
-      key[b][s] = (valid[s] && !isn) ? v[b][s] : inf;
-    }
-    any_nan[b] = __builtin_amdgcn_ballot_w64(bad) != 0;
-  }
-  // mean, shifted by c = v[1] (lane 1, slot 0), and the two-pass standard deviation; fixed order: the lane's slots
-  // ascending, then the wave butterfly
-  double acc[NB], c[NB], mean[NB], sd[NB];
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    c[b] = readlane_f64(v[b][0], 1);
-    c[b] = fabs(c[b]) < inf ? c[b] : 0.0;
-    acc[b] = 0.0;
-#pragma unroll
-    for (int s = 0; s < V; ++s) acc[b] += valid[s] ? v[b][s] - c[b] : 0.0;
-  }
-  ef_wave_sum<NB>(acc, lane);
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    mean[b] = c[b] + acc[b] / (double)n;
-    acc[b] = 0.0;
-#pragma unroll
-    for (int s = 0; s < V; ++s) {
-      const double d = v[b][s] - mean[b];
-      acc[b] += valid[s] ? d * d : 0.0;
-    }
-  }
-  ef_wave_sum<NB>(acc, lane);
-#pragma unroll
-  for (int b = 0; b < NB; ++b) sd[b] = sqrt(acc[b] / (double)(n - 1));
-  ef_sort<NB, V>(key, lane);
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    double* sb = st + b * NS;
-    const double point = readlane_f64(v[b][0], 0);
-    if (lane == 0) {
-      sb[0] = point;
-      sb[1] = any_nan[b] ? nan : mean[b];
-      sb[2] = any_nan[b] ? nan : sd[b];
-    }
-    for (int j = 0; j < ra.Q; ++j) {
-      const int i = (int)ra.qr[j].i;
-      const double g = ra.qr[j].g;
-      double qv = ef_quantile<V>(key[b], i, g, n);
-      qv = any_nan[b] ? nan : qv;
-      if (lane == 0) sb[3 + j] = qv;
-    }
-  }
-}
-
 template <int V, int NARM>
 __global__ void __launch_bounds__(kWave) regimen_choice_kernel(RgArgs ra, AffineLib lib) {
   extern __shared__ double rg_lds[];  // [kRgStage] staging, then the objective columns [K - 1][Rpad]
@@ -167,39 +101,10 @@ __global__ void __launch_bounds__(kWave) regimen_choice_kernel(RgArgs ra, Affine
   for (int s = 0; s < V; ++s) valid[s] = s * kWave + lane >= 1 && s * kWave + lane < ra.R;
 
   for (int64_t p = p_lo; p < p_hi; ++p) {
-    // ---- prologue: the interval maps of the lane's replicates (effect_bands_kernel's) ------------------------
-    double uu[INSITE_MAX_STATICS];
-#pragma unroll
-    for (int t = 0; t < INSITE_MAX_STATICS; ++t) uu[t] = t < lib.U ? ra.u[p * lib.U + t] : 0.0;
+    // ---- prologue: the interval maps of the lane's replicates (insite_affine.h) ------------------------------
     double PA[V][NARM], PB[V][NARM];
-#pragma unroll
-    for (int s = 0; s < V; ++s) {
-      const int r = s * kWave + lane;
-      const double* cb = ra.coef + (int64_t)(r < ra.R ? r : 0) * ra.A * lib.F;
-      double al[NARM], be[NARM];
-#pragma unroll
-      for (int a = 0; a < NARM; ++a) al[a] = be[a] = 0.0;
-#pragma unroll
-      for (int j = 0; j < INSITE_MAX_TERMS; ++j) {
-        if (j < lib.F) {
-          const int code = lib.ucode[j];
-          const double m = monomial_code(code & 0xffffff, uu);
-          const bool lin = (code >> 24) != 0;
-#pragma unroll
-          for (int a = 0; a < NARM; ++a) {
-            if (a < ra.A) {
-              const double c = cb[a * lib.F + j];
-              // a dropped term adds 0; a NaN coefficient is kept (insite_effect.h)
-              const double v = (fabs(c) > ra.drop || c != c) ? c * m : 0.0;
-              if (lin) be[a] += v;
-              else al[a] += v;
-            }
-          }
-        }
-      }
-#pragma unroll
-      for (int a = 0; a < NARM; ++a) interval_map(ra.method, ra.substeps, h, al[a], be[a], PA[s][a], PB[s][a]);
-    }
+    ensemble_maps<V, NARM>(lib, ra.coef, ra.u + p * lib.U, ra.R, ra.A, ra.drop, ra.method, ra.substeps, h, lane, PA,
+                           PB);
     const double y0 = ra.y0[p];
 
     // ---- phase 1: the objectives of every plan, the running minimum inside each replicate -------------------
@@ -283,14 +188,14 @@ __global__ void __launch_bounds__(kWave) regimen_choice_kernel(RgArgs ra, Affine
           v[0][s] = J[s];
           v[1][s] = g[s];
         }
-        rg_stats<2, V>(v, valid, lane, n, ra, stage);
+        ef_series_stats<2, V>(v, valid, lane, n, ra.Q, ra.qr, stage, 1);
       } else {
 #pragma unroll 1
         for (int sv = 0; sv < 2; ++sv) {
           double v[1][V];
 #pragma unroll
           for (int s = 0; s < V; ++s) v[0][s] = sv == 0 ? J[s] : g[s];
-          rg_stats<1, V>(v, valid, lane, n, ra, stage + sv * NS);
+          ef_series_stats<1, V>(v, valid, lane, n, ra.Q, ra.qr, stage + sv * NS, 1);
         }
       }
       // flush the plan's block: out[p, j, :, :], 2 (3 + Q) contiguous doubles
@@ -299,13 +204,6 @@ __global__ void __launch_bounds__(kWave) regimen_choice_kernel(RgArgs ra, Affine
       wave_lds_sync();
     }
   }
-}
-
-template <int V>
-void rg_launch_v(int na, dim3 grid, size_t lds, hipStream_t hs, const RgArgs& ra, const AffineLib& lib) {
-  if (na == 1) regimen_choice_kernel<V, 1><<<grid, kWave, lds, hs>>>(ra, lib);
-  else if (na == 2) regimen_choice_kernel<V, 2><<<grid, kWave, lds, hs>>>(ra, lib);
-  else regimen_choice_kernel<V, 4><<<grid, kWave, lds, hs>>>(ra, lib);
 }
 
 // a + b c in int64, or false when it does not fit (a, b, c >= 0)
@@ -330,9 +228,9 @@ int32_t insite_regimen_choice_f64(const double* y0, const double* u, const int8_
                                   int32_t n_replicates, const double* q, int32_t n_quantiles, int32_t* choice,
                                   double* win, double* out, int64_t ld_out, void* /*workspace*/,
                                   size_t /*workspace_bytes*/, void* stream) {
-  if (n_rows < 0 || T < 1 || n_arms < 1 || n_arms > INSITE_MAX_ARMS || substeps < 1 || !(dt >= 0.0) ||
-      n_replicates < 2 || check_quantiles(q, n_quantiles, INSITE_REGIMEN_MAX_QUANTILES) != INSITE_OK ||
-      n_plans < 1 || n_plans > INSITE_REGIMEN_MAX_PLANS ||
+  if (!ensemble_shape_ok(n_rows, T, n_arms, substeps, dt, n_replicates) ||
+      check_quantiles(q, n_quantiles, INSITE_REGIMEN_MAX_QUANTILES) != INSITE_OK || n_plans < 1 ||
+      n_plans > INSITE_REGIMEN_MAX_PLANS ||
       (sense != INSITE_REGIMEN_MINIMIZE && sense != INSITE_REGIMEN_MAXIMIZE))
     return INSITE_E_INVALID_ARG;
   // the strides: their lower bounds, and the largest element offset of every array must fit int64 (the kernel's index
@@ -348,12 +246,10 @@ int32_t insite_regimen_choice_f64(const double* y0, const double* u, const int8_
   const int64_t block = (int64_t)n_plans * 2 * (3 + n_quantiles);
   if (ld_out < block || !rg_mul_add(block, last_row, ld_out, &top) || !rg_mul_add(0, n_rows, (int64_t)n_plans, &top))
     return INSITE_E_INVALID_ARG;
-  if (method != INSITE_METHOD_EULER && method != INSITE_METHOD_RK4) return INSITE_E_UNSUPPORTED;
   AffineLib lib;
-  const int32_t st = build_affine_lib(exps, n_terms, n_statics, &lib);
-  if (st != INSITE_OK) return st;
-  if (n_replicates > INSITE_REGIMEN_MAX_REPLICATES) return INSITE_E_UNSUPPORTED;
-  if (n_rows == 0) return INSITE_OK;
+  const int32_t st =
+      ensemble_lib(method, exps, n_terms, n_statics, n_replicates, INSITE_REGIMEN_MAX_REPLICATES, &lib);
+  if (st != INSITE_OK || n_rows == 0) return st;
   if (!y0 || !plans || !w || !coef || !choice || !win || !out || (n_statics > 0 && !u)) return INSITE_E_INVALID_ARG;
 
   RgArgs ra;
@@ -383,19 +279,15 @@ int32_t insite_regimen_choice_f64(const double* y0, const double* u, const int8_
   ra.drop = drop_below;
   ra.sense = (double)sense;
   for (int j = 0; j < n_quantiles; ++j) ra.qr[j] = quantile_rank(q[j], n_replicates - 1);
-  const int v = n_replicates <= 64 ? 1 : (n_replicates <= 128 ? 2 : (n_replicates <= 256 ? 4 : 8));
-  ra.Rpad = v * kWave;
+  ra.Rpad = replicate_slots(n_replicates) * kWave;
   // staging + K - 1 columns: at most 40 + 15 x 512 doubles = 61760 bytes, below the 64 KiB a launch may ask for
   const size_t lds = sizeof(double) * ((size_t)kRgStage + (size_t)(n_plans - 1) * (size_t)ra.Rpad);
-  const int64_t blocks = n_rows < kRgMaxBlocks ? n_rows : kRgMaxBlocks;
-  ra.ppb = (n_rows + blocks - 1) / blocks;
+  ra.ppb = rows_per_block(n_rows);
   const dim3 grid((unsigned)((n_rows + ra.ppb - 1) / ra.ppb));
   hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
-  const int na = n_arms <= 1 ? 1 : (n_arms <= 2 ? 2 : 4);
-  if (v == 1) rg_launch_v<1>(na, grid, lds, hs, ra, lib);
-  else if (v == 2) rg_launch_v<2>(na, grid, lds, hs, ra, lib);
-  else if (v == 4) rg_launch_v<4>(na, grid, lds, hs, ra, lib);
-  else rg_launch_v<8>(na, grid, lds, hs, ra, lib);
+  with_slots(n_replicates, n_arms, [&](auto v, auto narm) {
+    regimen_choice_kernel<v(), narm()><<<grid, kWave, lds, hs>>>(ra, lib);
+  });
   return launch_status();
 }
 

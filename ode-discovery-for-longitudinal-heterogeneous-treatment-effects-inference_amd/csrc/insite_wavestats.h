@@ -1,10 +1,14 @@
 // insite_wavestats.h — the one definition of the order statistics and moments one wave takes over the bootstrap
 // replicates it holds in registers (lane l, slot s = replicate s 64 + l; V = R_pad / 64 slots per lane): the lane
-// exchanges, the fixed-order wave sums, the in-register bitonic sort, the read of a sorted rank and the quantile of
-// include/insite_effect.h.  insite_effect.hip and insite_regimen.hip (§9j) include it: the statistics of
-// the regimen choice are the effect bands' "word for word" because they are the same code.
+// exchanges, the fixed-order wave sums, the in-register bitonic sort, the read of a sorted rank and, built on them,
+// ef_series_stats: the point value, moments, quantiles and NaN rule of include/insite_effect.h.  effect_bands_kernel
+// (insite_effect.hip) and regimen_choice_kernel (insite_regimen.hip, §9j) both call ef_series_stats
+// and differ only in the stride of the staging writes, so the regimen statistics are the effect bands' by
+// construction.  The quantile interpolation is insite_affine.h's quantile_interp, shared with the cohort finalize.
 // insite_common.h's convention: an anonymous namespace, each translation unit gets its own internal copy.
 #pragma once
+#include <limits>
+
 #include "insite_affine.h"
 
 namespace {
@@ -171,15 +175,73 @@ __device__ __forceinline__ double ef_rank_value(const double (&key)[V], int i) {
   return readlane_f64(x[0], i >> LV);
 }
 
-// the quantile of rank (i, g) (insite_affine.h's quantile_rank of q over n keys) of the n sorted keys: insite_effect.h's
-// formula, s[i] when g == 0 or s[i] == hi, else s[i] + g (hi - s[i]) with hi = s[min(i + 1, n - 1)].
-// effect_bands_kernel keeps these three lines written out: calling them through this function gave the same values
-// but another register allocation of that kernel, and its move into this header was to change no instruction.
-template <int V>
-__device__ __forceinline__ double ef_quantile(const double (&key)[V], int i, double g, int n) {
-  const double lo = ef_rank_value<V>(key, i);
-  const double hi = ef_rank_value<V>(key, i + 1 < n ? i + 1 : n - 1);
-  return (g == 0.0 || lo == hi) ? lo : lo + g * (hi - lo);
+// The statistics of NB series over the replicates 1..R-1 = the valid slots (insite_effect.h: the point model's value,
+// the mean shifted by replicate 1's value, the two-pass standard deviation with ddof 1, the Q quantiles of ranks qr
+// over the n = R - 1 keys, and the NaN rule: one NaN among the valid values makes everything but the point NaN).
+// Lane 0 writes statistic t of series b to stage[(b (3 + Q) + t) stride]; the NB sorts and reductions are independent
+// chains issued together.
+template <int NB, int V>
+__device__ __forceinline__ void ef_series_stats(const double (&v)[NB][V], const bool (&valid)[V], int lane, int n,
+                                                int Q, const QuantileRank* qr, double* stage, int stride) {
+  const double inf = std::numeric_limits<double>::infinity();
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  double key[NB][V];
+  bool any_nan[NB];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    bool bad = false;
+#pragma unroll
+    for (int s = 0; s < V; ++s) {
+      const bool isn = v[b][s] != v[b][s];
+      bad = bad || (valid[s] && isn);
+      key[b][s] = (valid[s] && !isn) ? v[b][s] : inf;
+    }
+    any_nan[b] = __builtin_amdgcn_ballot_w64(bad) != 0;
+  }
+  // mean, shifted by c = v[1] (lane 1, slot 0), and the two-pass standard deviation; fixed order: the lane's slots
+  // ascending, then the wave butterfly
+  double acc[NB], c[NB], mean[NB], sd[NB];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    c[b] = readlane_f64(v[b][0], 1);
+    c[b] = fabs(c[b]) < inf ? c[b] : 0.0;
+    acc[b] = 0.0;
+#pragma unroll
+    for (int s = 0; s < V; ++s) acc[b] += valid[s] ? v[b][s] - c[b] : 0.0;
+  }
+  ef_wave_sum<NB>(acc, lane);
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    mean[b] = c[b] + acc[b] / (double)n;
+    acc[b] = 0.0;
+#pragma unroll
+    for (int s = 0; s < V; ++s) {
+      const double d = v[b][s] - mean[b];
+      acc[b] += valid[s] ? d * d : 0.0;
+    }
+  }
+  ef_wave_sum<NB>(acc, lane);
+#pragma unroll
+  for (int b = 0; b < NB; ++b) sd[b] = sqrt(acc[b] / (double)(n - 1));
+  ef_sort<NB, V>(key, lane);
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    double* st = stage + b * (3 + Q) * stride;
+    const double point = readlane_f64(v[b][0], 0);
+    if (lane == 0) {
+      st[0] = point;
+      st[stride] = any_nan[b] ? nan : mean[b];
+      st[2 * stride] = any_nan[b] ? nan : sd[b];
+    }
+    for (int j = 0; j < Q; ++j) {
+      const int i = (int)qr[j].i;
+      const double lo = ef_rank_value<V>(key[b], i);
+      const double hi = ef_rank_value<V>(key[b], i + 1 < n ? i + 1 : n - 1);
+      double qv = quantile_interp(lo, hi, qr[j].g);
+      qv = any_nan[b] ? nan : qv;
+      if (lane == 0) st[(3 + j) * stride] = qv;
+    }
+  }
 }
 
 }  // namespace

@@ -908,6 +908,13 @@ def _check_ensemble(y0, u, arm_a, arm_b, coef, lib, T, max_replicates):
         _dev(name, arm, torch.int8, 2)
         if arm.size(0) != N or arm.size(1) < T:
             raise ValueError(f"{name} must be [N, >=T]")
+    R, A = _check_statics_coef(u, coef, lib, N, max_replicates)
+    return N, T, R, A
+
+
+def _check_statics_coef(u, coef, lib, N, max_replicates):
+    """The statics u [N, n_statics] and the ensemble coef [R, n_arms, F] with R up to ``max_replicates``, in this
+    order: what every consumer of the ensemble checks after its own plans.  Returns (R, A)."""
     if lib.n_statics:
         _dev("u", u, torch.float64, 2)
         if u.size(0) != N or u.size(1) != lib.n_statics or u.stride(0) != lib.n_statics:
@@ -920,7 +927,7 @@ def _check_ensemble(y0, u, arm_a, arm_b, coef, lib, T, max_replicates):
         raise ValueError(f"n_arms must be in [1, {_lib.MAX_ARMS}]")
     if not 2 <= R <= max_replicates:
         raise ValueError(f"n_replicates must be in [2, {max_replicates}] (replicate 0 is the point model)")
-    return N, T, R, A
+    return R, A
 
 
 def _method(method, substeps):
@@ -1024,18 +1031,8 @@ def _prep_regimen_choice(y0, u, plans, coef, lib, dt, quantiles, weights, cost, 
         _dev("cost", cost, torch.float64, 1)
         if cost.numel() != K or not cost.is_contiguous():
             raise ValueError("cost must be a contiguous f64 [K] tensor")
-    if lib.n_statics:
-        _dev("u", u, torch.float64, 2)
-        if u.size(0) != N or u.size(1) != lib.n_statics or u.stride(0) != lib.n_statics:
-            raise ValueError("u must be a contiguous [N, n_statics] tensor")
-    _dev("coef", coef, torch.float64, 3)
-    if not coef.is_contiguous() or coef.size(-1) != lib.n_terms:
-        raise ValueError("coef must be a contiguous [R, n_arms, F] tensor")
-    R, A, F = coef.size(0), coef.size(1), lib.n_terms
-    if not 1 <= A <= _lib.MAX_ARMS:
-        raise ValueError(f"n_arms must be in [1, {_lib.MAX_ARMS}]")
-    if not 2 <= R <= _lib.REGIMEN_MAX_REPLICATES:
-        raise ValueError(f"n_replicates must be in [2, {_lib.REGIMEN_MAX_REPLICATES}] (replicate 0 is the point model)")
+    R, A = _check_statics_coef(u, coef, lib, N, _lib.REGIMEN_MAX_REPLICATES)
+    F = lib.n_terms
     q = _quantiles(quantiles, _lib.REGIMEN_MAX_QUANTILES)
     m, sub = _method(method, substeps)
     dev = y0.device
