@@ -16,8 +16,9 @@
 //                          to its workspace slot.
 //   cohort_reduce_kernel   thread = one element of sums / wsum: the chunks' partials in chunk order.
 //   cohort_finalize_kernel block = (group, step): the means of the 1 or 3 series, per series the fixed-order mean and
-//                          two-pass deviation and a bitonic sort of the R_pad keys in LDS; the quantile interpolation
-//                          is insite_affine.h's quantile_interp, as are the host's common checks and NARM choice.
+//                          two-pass deviation and a bitonic sort of the R_pad keys in LDS (insite_blockstats.h's
+//                          co_block_series_stats, shared with policy_finalize_kernel); the host's common checks and
+//                          NARM choice are insite_affine.h's.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -26,6 +27,7 @@
 #include <limits>
 
 #include "insite_affine.h"
+#include "insite_blockstats.h"
 #include "insite_cohort.h"
 
 namespace {
@@ -100,21 +102,6 @@ struct CoArgs {
 };
 
 constexpr int kCoWin = 64;  // steps whose arms one load brings in (one per lane)
-
-// the arms of one 64-step window as bit masks: bit k of m[a - 1] = (the arm of step k is a); no bit: arm 0
-template <int NARM>
-struct CoArmMask {
-  uint64_t m[NARM > 1 ? NARM - 1 : 1];
-};
-
-template <int NARM>
-__device__ __forceinline__ CoArmMask<NARM> co_arm_mask(int v, int n_arms) {
-  CoArmMask<NARM> r;
-  r.m[0] = 0;
-#pragma unroll
-  for (int a = 1; a < NARM; ++a) r.m[a - 1] = __builtin_amdgcn_ballot_w64(v == a && a < n_arms);
-  return r;
-}
 
 // one step: the candidate of every arm, then the step's (wave-uniform) choice among the results -- NARM FMAs and
 // NARM - 1 selects of one double, against 2 (NARM - 1) selects and one FMA when the map is selected first
@@ -357,19 +344,6 @@ struct CoFinArgs {
   QuantileRank qr[INSITE_COHORT_MAX_QUANTILES];
 };
 
-// the sum of the threads' values in a fixed order (a tree over red[]); every thread gets it
-__device__ __forceinline__ double co_block_sum(double v, double* red) {
-  const int t = threadIdx.x;
-  __syncthreads();
-  red[t] = v;
-  __syncthreads();
-  for (int o = kCoFinBlock / 2; o > 0; o >>= 1) {
-    if (t < o) red[t] += red[t + o];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 // block = (group, step).  key: R_pad doubles of dynamic LDS.
 __global__ void __launch_bounds__(kCoFinBlock) cohort_finalize_kernel(CoFinArgs fa) {
   extern __shared__ double key[];
@@ -377,11 +351,9 @@ __global__ void __launch_bounds__(kCoFinBlock) cohort_finalize_kernel(CoFinArgs 
   const int t = threadIdx.x;
   const int k = blockIdx.x % fa.T;
   const int g = blockIdx.x / fa.T;
-  const int n = fa.R - 1;
   const int NS = 3 + fa.Q;
   const int S = fa.nser == 2 ? 3 : 1;
   const double inf = std::numeric_limits<double>::infinity();
-  const double nan = std::numeric_limits<double>::quiet_NaN();
   for (int sv = 0; sv < S; ++sv) {
     __syncthreads();
     // the means of the series; slots R.. of the padding are +Inf
@@ -397,54 +369,9 @@ __global__ void __launch_bounds__(kCoFinBlock) cohort_finalize_kernel(CoFinArgs 
       }
       key[r] = v;
     }
-    const bool any_nan = __syncthreads_or(bad) != 0;
-    const double point = key[0];
-    double c = key[1];
-    c = fabs(c) < inf ? c : 0.0;
-    // mean, shifted by c, and the two-pass deviation; fixed order: the thread's replicates ascending, then the tree
-    double a = 0.0;
-    for (int r = t; r < fa.R; r += kCoFinBlock) a += r >= 1 ? key[r] - c : 0.0;
-    const double mean = c + co_block_sum(a, red) / (double)n;
-    a = 0.0;
-    for (int r = t; r < fa.R; r += kCoFinBlock) {
-      const double d = key[r] - mean;
-      a += r >= 1 ? d * d : 0.0;
-    }
-    const double sd = sqrt(co_block_sum(a, red) / (double)(n - 1));
-    __syncthreads();
-    // the keys: the point model and NaN go to +Inf (with a NaN every quantile is NaN anyway)
-    for (int r = t; r < fa.R; r += kCoFinBlock) {
-      const double v = key[r];
-      key[r] = (r >= 1 && v == v) ? v : inf;
-    }
-    __syncthreads();
-    for (int kk = 2; kk <= fa.rpad; kk <<= 1) {
-      for (int j = kk >> 1; j > 0; j >>= 1) {
-        for (int i = t; i < fa.rpad; i += kCoFinBlock) {
-          const int l = i ^ j;
-          if (l > i) {
-            const double x = key[i], y = key[l];
-            const bool up = (i & kk) == 0;
-            if ((x > y) == up) {
-              key[i] = y;
-              key[l] = x;
-            }
-          }
-        }
-        __syncthreads();
-      }
-    }
     double* o = fa.out + (((int64_t)g * S + sv) * NS) * fa.ldo + k;
-    if (t == 0) {
-      o[0] = point;
-      o[fa.ldo] = any_nan ? nan : mean;
-      o[2 * fa.ldo] = any_nan ? nan : sd;
-    }
-    if (t < fa.Q) {
-      const int i = (int)fa.qr[t].i;
-      const double qv = quantile_interp(key[i], key[i + 1 < n ? i + 1 : n - 1], fa.qr[t].g);
-      o[(3 + t) * fa.ldo] = any_nan ? nan : qv;
-    }
+    co_block_series_stats<kCoFinBlock>(key, red, fa.R, fa.rpad, fa.Q, fa.qr, bad,
+                                       [&](int i, double x) { o[i * fa.ldo] = x; });
   }
 }
 

@@ -38,6 +38,8 @@ COHORT_WEIGHT_NONE, COHORT_WEIGHT_POISSON = 0, 1
 # include/insite_regimen.h
 REGIMEN_ABI_VERSION, REGIMEN_MAX_REPLICATES, REGIMEN_MAX_QUANTILES, REGIMEN_MAX_PLANS = 1, 512, 16, 16
 REGIMEN_MINIMIZE, REGIMEN_MAXIMIZE = 1, -1
+# include/insite_policy.h
+POLICY_ABI_VERSION, POLICY_MAX_REPLICATES, POLICY_MAX_PLANS, POLICY_MAX_GROUPS, POLICY_MAX_QUANTILES = 1, 4096, 16, 64, 16
 METHOD_EULER, METHOD_RK4 = 0, 1
 LAYOUT_PATIENT_MAJOR, LAYOUT_TIME_MAJOR, LAYOUT_TIME_MAJOR_BITS, LAYOUT_PATIENT_MAJOR_BITS = 0, 1, 2, 3
 MAX_TERMS, MAX_STATICS, MAX_ARMS, MAX_STATE_DEGREE = 9, 3, 4, 1
@@ -140,6 +142,16 @@ REGIMEN_EXPORTS = (
     "insite_regimen_abi_version",
     "insite_regimen_workspace_bytes",
     "insite_regimen_choice_f64",
+)
+
+# the extension header include/insite_policy.h (same shared library, its own ABI version; a list of its own:
+# the seven lists above are pinned by tests)
+POLICY_EXPORTS = (
+    "insite_policy_abi_version",
+    "insite_policy_workspace_bytes",
+    "insite_policy_sums_f64",
+    "insite_policy_finalize_f64",
+    "insite_policy_value_f64",
 )
 
 
@@ -299,6 +311,17 @@ _SIGNATURES = {
     "insite_regimen_choice_f64": (_c_i32, [_vp, _vp, _vp, _c_i32, _c_i64, _c_i64, _vp, _c_i64, _vp, _c_i32, _vp, _vp,
                                            _c_i32, _c_i64, _c_i32, _c_i32, _c_i32, _c_f64, _c_i32, _c_i32, _c_f64,
                                            _c_i32, _vp, _c_i32, _vp, _vp, _vp, _c_i64, _vp, _c_size, _vp]),
+    # insite_policy.h
+    "insite_policy_abi_version": (_c_i32, []),
+    "insite_policy_workspace_bytes": (_c_size, [_c_i64, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32]),
+    "insite_policy_sums_f64": (_c_i32, [_vp, _vp, _vp, _c_i32, _c_i64, _c_i64, _vp, _c_i64, _vp, _c_i32, _vp, _vp, _c_i32, _c_i64,
+                                        _c_i32, _c_i32, _c_i32, _c_f64, _c_i32, _c_i32, _c_f64, _c_i32, _vp, _c_i32,
+                                        _c_i32, ctypes.c_uint32, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_size, _vp]),
+    "insite_policy_finalize_f64": (_c_i32, [_vp, _vp, _c_i32, _c_i32, _c_i32, _c_i32, _vp, _c_i32, _vp, _c_i64, _vp,
+                                            _vp, _vp]),
+    "insite_policy_value_f64": (_c_i32, [_vp, _vp, _vp, _c_i32, _c_i64, _c_i64, _vp, _c_i64, _vp, _c_i32, _vp, _vp, _c_i32, _c_i64,
+                                        _c_i32, _c_i32, _c_i32, _c_f64, _c_i32, _c_i32, _c_f64, _c_i32, _vp, _c_i32,
+                                        _c_i32, ctypes.c_uint32, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_i32, _vp, _c_i64, _vp, _vp, _vp, _c_size, _vp]),
 }
 
 # (getter, the version these bindings were written for, the label of the mismatch message)
@@ -310,6 +333,7 @@ _ABI_VERSIONS = (
     ("insite_effect_abi_version", EFFECT_ABI_VERSION, "effect "),
     ("insite_cohort_abi_version", COHORT_ABI_VERSION, "cohort "),
     ("insite_regimen_abi_version", REGIMEN_ABI_VERSION, "regimen "),
+    ("insite_policy_abi_version", POLICY_ABI_VERSION, "policy "),
 )
 
 

@@ -121,3 +121,66 @@ def from_regimen(choice: torch.Tensor, win: torch.Tensor, out: torch.Tensor, q, 
     res[0, loc] = (o[0, loc] - sh) / scale
     return RegimenChoiceResult(choice=choice, win=win, point=res[:, 0], mean=res[:, 1], std=res[:, 2],
                                quantiles=res[:, 3:], q=tuple(float(v) for v in q))
+
+
+def policy_series(n_plans: int) -> tuple:
+    """The names of the 2 K + 6 series of ``ops.policy_value`` in the order of include/insite_policy.h."""
+    K = int(n_plans)
+    return (tuple(f"value_{j}" for j in range(K))
+            + ("personalised", "rule", "best_fixed", "gain_personalised", "gain_rule", "optimism")
+            + tuple(f"share_{j}" for j in range(K)))
+
+
+@dataclasses.dataclass
+class PolicyValueResult:
+    """The cohort value of a personalised choice among K plans of ``ops.policy_value`` (include/insite_policy.h,
+    DESIGN.md §9k).  ``series``: ``policy_series(K)`` -- value_j (everyone gets plan j), personalised (every row its
+    own best plan, re-derived inside each replicate), rule (the fixed per-row ``rule`` under each replicate's model),
+    best_fixed (the best single plan of the replicate), gain_personalised = best_fixed - personalised, gain_rule =
+    best_fixed - rule and optimism = rule - personalised (signed by the sense: the first and the last are >= 0, gain_rule
+    is negative where the rule is worse than the best single plan), share_j (the weight share
+    of the rows whose best plan is j).  ``point``, ``mean``, ``std`` [S, G]: per group the point model's value and the
+    mean / standard deviation (n - 1 divisor) over the replicates 1..R-1; ``quantiles`` [S, Q, G] in the order of
+    ``q``.  ``fixwin`` [G, K]: the share of the replicates in which plan j is the best fixed plan; ``best_fixed``
+    int32 [G]: the point model's (-1: it has a NaN value); ``rule`` int32 [N]; ``weight_sum`` [R, G].
+    ``result["optimism"]`` gives one series as a dict, ``result.share`` the K share series as [K, G] statistics."""
+    point: torch.Tensor
+    mean: torch.Tensor
+    std: torch.Tensor
+    quantiles: torch.Tensor
+    fixwin: torch.Tensor
+    best_fixed: torch.Tensor
+    rule: torch.Tensor
+    weight_sum: torch.Tensor
+    q: tuple
+    series: tuple
+    n_plans: int
+
+    def __getitem__(self, name: str) -> dict:
+        i = self.series.index(name)
+        return {"point": self.point[i], "mean": self.mean[i], "std": self.std[i], "quantiles": self.quantiles[i]}
+
+    @property
+    def share(self) -> dict:
+        lo = self.n_plans + 6
+        return {"point": self.point[lo:], "mean": self.mean[lo:], "std": self.std[lo:],
+                "quantiles": self.quantiles[lo:].transpose(0, 1)}
+
+
+def from_policy(out: torch.Tensor, fixwin: torch.Tensor, best_fixed: torch.Tensor, rule: torch.Tensor,
+                wsum: torch.Tensor, q, shift: float = 0.0, scale: float = 1.0) -> PolicyValueResult:
+    """``ops.policy_value``'s outputs as a ``PolicyValueResult`` in the scale (x - shift) / scale: the locations
+    (point, mean, quantiles) of the value, personalised, rule and best_fixed series are shifted and divided, their
+    standard deviations and every statistic of the three differences (the shift cancels) are divided only, the shares
+    are left as they are.  ``shift``: the mean times the weight total of a row's steps."""
+    if out.dim() != 3 or out.size(1) < 8 or out.size(1) % 2 or out.size(2) != 3 + len(q):
+        raise ValueError("out must be [G, 2 K + 6, 3 + Q]")
+    K = out.size(1) // 2 - 3
+    o = out.permute(1, 2, 0)                        # [S, 3 + Q, G]
+    res = o.clone()
+    loc = [0, 1] + list(range(3, o.size(1)))        # point, mean and quantiles
+    res[:K + 6] = o[:K + 6] / scale
+    res[:K + 3, loc] = (o[:K + 3, loc] - shift) / scale
+    return PolicyValueResult(point=res[:, 0], mean=res[:, 1], std=res[:, 2], quantiles=res[:, 3:], fixwin=fixwin,
+                             best_fixed=best_fixed, rule=rule, weight_sum=wsum, q=tuple(float(v) for v in q),
+                             series=policy_series(K), n_plans=K)

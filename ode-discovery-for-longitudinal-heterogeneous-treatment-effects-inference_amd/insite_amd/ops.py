@@ -992,10 +992,10 @@ def plan_effect_bands(y0, u, arm_a, arm_b, coef, lib, dt, quantiles, method="eul
     return Plan(name, args, dev, out, keep)
 
 
-def _prep_regimen_choice(y0, u, plans, coef, lib, dt, quantiles, weights, cost, maximize, method, substeps, drop_below,
-                         T, out, workspace):
-    """Validate the inputs of the regimen choice and pack the C arguments (insite_regimen.h)."""
-    L = _lib.load()
+def _check_plans_weights(y0, plans, weights, cost, T, max_plans):
+    """What the regimen choice and the policy value check first: y0 [N], the candidate plans int8 [K, T] (shared by
+    the rows) or [K, N, >=T], the step weights f64 [T] or [N, >=T] and cost f64 [K] or None.  Returns
+    (N, K, T, plan_stride, ld_plan, ld_w)."""
     _dev("y0", y0, torch.float64, 1)
     N = y0.numel()
     if not isinstance(plans, torch.Tensor) or not plans.is_cuda:
@@ -1004,8 +1004,8 @@ def _prep_regimen_choice(y0, u, plans, coef, lib, dt, quantiles, weights, cost, 
         raise ValueError("plans must be int8 [K, T] (shared by the rows) or [K, N, >=T]")
     _dev("plans", plans, torch.int8, plans.dim())
     K = plans.size(0)
-    if not 1 <= K <= _lib.REGIMEN_MAX_PLANS:
-        raise ValueError(f"between 1 and {_lib.REGIMEN_MAX_PLANS} plans expected, got {K}")
+    if not 1 <= K <= max_plans:
+        raise ValueError(f"between 1 and {max_plans} plans expected, got {K}")
     T = plans.size(-1) if T is None else int(T)
     if T < 1 or plans.size(-1) < T:
         raise ValueError("T must be >= 1 and the plans must hold at least T steps")
@@ -1031,6 +1031,14 @@ def _prep_regimen_choice(y0, u, plans, coef, lib, dt, quantiles, weights, cost, 
         _dev("cost", cost, torch.float64, 1)
         if cost.numel() != K or not cost.is_contiguous():
             raise ValueError("cost must be a contiguous f64 [K] tensor")
+    return N, K, T, plan_stride, ld_plan, ld_w
+
+
+def _prep_regimen_choice(y0, u, plans, coef, lib, dt, quantiles, weights, cost, maximize, method, substeps, drop_below,
+                         T, out, workspace):
+    """Validate the inputs of the regimen choice and pack the C arguments (insite_regimen.h)."""
+    L = _lib.load()
+    N, K, T, plan_stride, ld_plan, ld_w = _check_plans_weights(y0, plans, weights, cost, T, _lib.REGIMEN_MAX_PLANS)
     R, A = _check_statics_coef(u, coef, lib, N, _lib.REGIMEN_MAX_REPLICATES)
     F = lib.n_terms
     q = _quantiles(quantiles, _lib.REGIMEN_MAX_QUANTILES)
@@ -1218,6 +1226,158 @@ def plan_cohort_effect(y0, u, arm_a, arm_b, coef, lib, dt, quantiles, group=None
     name, args, dev, outs, keep = _prep_cohort(y0, u, arm_a, arm_b, coef, lib, dt, quantiles, group, n_groups,
                                                weighting, seed, patient_offset, method, substeps, drop_below, T, out,
                                                ws, None)
+    return Plan(name, args, dev, outs, keep)
+
+
+def _policy_stats_out(out, G, K, Q, dev):
+    """out [G, 2 K + 6, >= 3 + Q] (the statistics may be padded, everything else dense) and its leading dimension."""
+    S, NS = 2 * K + 6, 3 + Q
+    if out is None:
+        return torch.empty((G, S, NS), dtype=torch.float64, device=dev), NS
+    _dev("out", out, torch.float64, 3)
+    ld = out.stride(1)
+    if tuple(out.shape) != (G, S, NS) or ld < NS or (G > 1 and out.stride(0) != S * ld):
+        raise ValueError(f"out must be {(G, S, NS)} with a dense leading dimension (the statistics may be padded)")
+    return out, ld
+
+
+def _prep_policy(y0, u, plans, coef, lib, dt, quantiles, weights, cost, maximize, rule, group, n_groups, weighting,
+                 seed, patient_offset, method, substeps, drop_below, T, out, workspace, sums_out):
+    """Validate the inputs of the policy value and pack the C arguments (insite_policy.h); ``quantiles`` None: the
+    sums call alone."""
+    L = _lib.load()
+    N, K, T, plan_stride, ld_plan, ld_w = _check_plans_weights(y0, plans, weights, cost, T, _lib.POLICY_MAX_PLANS)
+    R, A = _check_statics_coef(u, coef, lib, N, _lib.POLICY_MAX_REPLICATES)
+    F = lib.n_terms
+    G = int(n_groups)
+    if not 1 <= G <= _lib.POLICY_MAX_GROUPS:
+        raise ValueError(f"n_groups must be in [1, {_lib.POLICY_MAX_GROUPS}]")
+    if group is not None:
+        _dev("group", group, torch.int32, 1)
+        if group.numel() != N:
+            raise ValueError("group must have one entry per row")
+    if weighting not in COHORT_WEIGHTINGS:
+        raise ValueError(f"weighting must be one of {sorted(COHORT_WEIGHTINGS)}")
+    if not 0 <= int(seed) < 2 ** 32:
+        raise ValueError("seed must be a uint32")
+    if int(patient_offset) < 0:
+        raise ValueError("patient_offset must be >= 0")
+    m, sub = _method(method, substeps)
+    dev = y0.device
+    rule_out = None
+    if rule is not None:
+        _dev("rule", rule, torch.int32, 1)
+        if rule.numel() != N or not rule.is_contiguous():
+            raise ValueError("rule must be a contiguous int32 tensor with one entry per row")
+    else:
+        rule_out = torch.full((N,), -1, dtype=torch.int32, device=dev)
+    C = 2 * K + 2
+    if sums_out is None:
+        sums_out = (torch.zeros((R, G, C), dtype=torch.float64, device=dev),
+                    torch.zeros((R, G), dtype=torch.float64, device=dev))
+    sums, wsum = sums_out
+    _dev("sums", sums, torch.float64, 3)
+    _dev("wsum", wsum, torch.float64, 2)
+    if tuple(sums.shape) != (R, G, C) or not sums.is_contiguous():
+        raise ValueError(f"sums must be a contiguous {(R, G, C)} tensor")
+    if tuple(wsum.shape) != (R, G) or not wsum.is_contiguous():
+        raise ValueError(f"wsum must be a contiguous {(R, G)} tensor")
+    ws_bytes = L.insite_policy_workspace_bytes(N, T, A, F, R, G, K)
+    ws = _ws(workspace, dev, "scratch").get(ws_bytes, dev)
+    tab = lib.ctypes_table()
+    head = (_p(y0), _p(u) if lib.n_statics else ctypes.c_void_p(0), _p(plans), K, plan_stride, ld_plan, _p(weights),
+            ld_w, _p(cost), _lib.REGIMEN_MAXIMIZE if maximize else _lib.REGIMEN_MINIMIZE, _p(coef),
+            tab.ctypes.data_as(ctypes.c_void_p), F, N, T, lib.n_statics, A, float(dt), m, sub, float(drop_below), R,
+            _p(group), G, COHORT_WEIGHTINGS[weighting], int(seed), int(patient_offset), _p(rule), _p(rule_out),
+            _p(sums), _p(wsum))
+    keep = (y0, u, plans, weights, cost, coef, group, rule, rule_out, tab, ws, sums, wsum)
+    the_rule = rule if rule is not None else rule_out
+    if quantiles is None:
+        return "insite_policy_sums_f64", head + (_p(ws), ws.numel()), dev, (sums, wsum, the_rule), keep
+    q = _quantiles(quantiles, _lib.POLICY_MAX_QUANTILES)
+    out, ld_out = _policy_stats_out(out, G, K, q.size, dev)
+    fixwin = torch.zeros((G, K), dtype=torch.float64, device=dev)
+    best_fixed = torch.full((G,), -1, dtype=torch.int32, device=dev)
+    args = head + (q.ctypes.data_as(ctypes.c_void_p), q.size, _p(out), ld_out, _p(fixwin), _p(best_fixed), _p(ws),
+                   ws.numel())
+    return ("insite_policy_value_f64", args, dev, (out, fixwin, best_fixed, the_rule, sums, wsum),
+            keep + (q, out, fixwin, best_fixed))
+
+
+def policy_sums(y0: torch.Tensor, u: torch.Tensor, plans: torch.Tensor, coef: torch.Tensor, lib: PolyLibrary,
+                dt: float, weights: torch.Tensor, cost: torch.Tensor | None = None, maximize: bool = False,
+                rule: torch.Tensor | None = None, group: torch.Tensor | None = None, n_groups: int = 1,
+                weighting: str = "poisson", seed: int = 0, patient_offset: int = 0, method: str = "euler5",
+                substeps: int | None = None, drop_below: float = 1e-3, T: int | None = None,
+                out: tuple | None = None, workspace: Workspace | None = None):
+    """The weighted objective sums of a cohort or of one shard of it (insite_policy_sums_f64):
+    (sums [R, G, 2 K + 2], wsum [R, G], rule int32 [N]).  Columns of sums: K fixed-plan values, the personalised rule
+    re-derived in the replicate, the given ``rule`` (None: the point model's choice, computed and returned), K
+    allocation counts.  sums and wsum are additive over shards (``patient_offset``: the index of row 0 in the whole
+    cohort); ``policy_finalize`` turns their total into the statistics.  With no rows nothing is written: fresh
+    outputs are zero."""
+    return _run(_prep_policy(y0, u, plans, coef, lib, dt, None, weights, cost, maximize, rule, group, n_groups,
+                             weighting, seed, patient_offset, method, substeps, drop_below, T, None, workspace, out))
+
+
+def policy_finalize(sums: torch.Tensor, wsum: torch.Tensor, quantiles, maximize: bool = False,
+                    out: torch.Tensor | None = None):
+    """The statistics of the 2 K + 6 series from ``policy_sums``' (all-reduced) arrays (insite_policy_finalize_f64):
+    (out [G, 2 K + 6, 3 + Q], fixwin [G, K], best_fixed int32 [G])."""
+    L = _lib.load()
+    _dev("sums", sums, torch.float64, 3)
+    _dev("wsum", wsum, torch.float64, 2)
+    R, G, C = sums.shape
+    if (not sums.is_contiguous() or not wsum.is_contiguous() or tuple(wsum.shape) != (R, G) or C < 4 or C % 2
+            or C // 2 - 1 > _lib.POLICY_MAX_PLANS):
+        raise ValueError(f"sums / wsum must be contiguous [R, G, 2 K + 2] / [R, G] tensors, K <= {_lib.POLICY_MAX_PLANS}")
+    K = C // 2 - 1
+    if not 2 <= R <= _lib.POLICY_MAX_REPLICATES:
+        raise ValueError(f"n_replicates must be in [2, {_lib.POLICY_MAX_REPLICATES}] (replicate 0 is the point model)")
+    if not 1 <= G <= _lib.POLICY_MAX_GROUPS:
+        raise ValueError(f"n_groups must be in [1, {_lib.POLICY_MAX_GROUPS}]")
+    q = _quantiles(quantiles, _lib.POLICY_MAX_QUANTILES)
+    dev = sums.device
+    out, ld_out = _policy_stats_out(out, G, K, q.size, dev)
+    fixwin = torch.zeros((G, K), dtype=torch.float64, device=dev)
+    best_fixed = torch.full((G,), -1, dtype=torch.int32, device=dev)
+    st = L.insite_policy_finalize_f64(_p(sums), _p(wsum), R, G, K,
+                                      _lib.REGIMEN_MAXIMIZE if maximize else _lib.REGIMEN_MINIMIZE,
+                                      q.ctypes.data_as(ctypes.c_void_p), q.size, _p(out), ld_out, _p(fixwin),
+                                      _p(best_fixed), _stream(dev))
+    _lib.check("insite_policy_finalize_f64", st)
+    return out, fixwin, best_fixed
+
+
+def policy_value(y0: torch.Tensor, u: torch.Tensor, plans: torch.Tensor, coef: torch.Tensor, lib: PolyLibrary,
+                 dt: float, quantiles, weights: torch.Tensor, cost: torch.Tensor | None = None,
+                 maximize: bool = False, rule: torch.Tensor | None = None, group: torch.Tensor | None = None,
+                 n_groups: int = 1, weighting: str = "poisson", seed: int = 0, patient_offset: int = 0,
+                 method: str = "euler5", substeps: int | None = None, drop_below: float = 1e-3, T: int | None = None,
+                 out: torch.Tensor | None = None, workspace: Workspace | None = None):
+    """What a cohort gains from a personalised choice among K plans, with bootstrap bands (insite_policy_value_f64,
+    DESIGN.md §9k).
+
+    ``plans``, ``weights``, ``cost``, ``maximize`` as in ``regimen_choice``; ``group``, ``n_groups``, ``weighting``,
+    ``seed``, ``patient_offset`` as in ``cohort_effect``; ``rule`` int32 [N] (a plan per row) or None (the point
+    model's choice).  Returns (out [G, 2 K + 6, 3 + Q], fixwin [G, K], best_fixed int32 [G], rule int32 [N], sums
+    [R, G, 2 K + 2], wsum [R, G]).  Series of out: value_0..value_{K-1} (everyone gets plan j), personalised (every
+    row its best plan, re-derived inside each replicate), rule (the fixed rule under each replicate's model),
+    best_fixed, gain_personalised, gain_rule, optimism, share_0..share_{K-1}; each as the point model's value, then
+    mean, standard deviation (ddof 1) and the ``quantiles`` over the replicates 1..R-1.  The per-replicate objectives
+    never exist in memory.  With no rows nothing is written."""
+    return _run(_prep_policy(y0, u, plans, coef, lib, dt, quantiles, weights, cost, maximize, rule, group, n_groups,
+                             weighting, seed, patient_offset, method, substeps, drop_below, T, out, workspace, None))
+
+
+def plan_policy_value(y0, u, plans, coef, lib, dt, quantiles, weights, cost=None, maximize=False, rule=None,
+                      group=None, n_groups=1, weighting="poisson", seed=0, patient_offset=0, method="euler5",
+                      substeps=None, drop_below=1e-3, T=None, out=None, workspace=None) -> Plan:
+    """``policy_value`` as a prepared launch; ``plan.out`` = (out, fixwin, best_fixed, rule, sums, wsum)."""
+    ws = workspace.claim("scratch") if workspace is not None else Workspace("scratch")
+    name, args, dev, outs, keep = _prep_policy(y0, u, plans, coef, lib, dt, quantiles, weights, cost, maximize, rule,
+                                               group, n_groups, weighting, seed, patient_offset, method, substeps,
+                                               drop_below, T, out, ws, None)
     return Plan(name, args, dev, outs, keep)
 
 

@@ -662,8 +662,8 @@ class SINDY:
         """``average_effect`` for one plan (None: the dataset's own treatments): the one series "a"."""
         return self._cohort_average("predict_average", dataset, plan, None, False, groups, quantiles, resample, seed)
 
-    def _cohort_average(self, what, dataset, plan_a, plan_b, two, groups, quantiles, resample, seed):
-        coef = self._effect_coef(what, _lib.COHORT_MAX_REPLICATES)
+    def _resample(self, what, resample, seed):
+        """``resample`` / ``seed`` of the cohort-level calls -> (the row weighting, the seed of the Poisson counts)."""
         bs = self.bootstrap_
         if resample == "paired":
             if bs.seed is None:
@@ -677,6 +677,11 @@ class SINDY:
             weighting, use_seed = "none", 0
         else:
             raise ValueError(f"{what}: resample must be 'paired', 'independent' or None")
+        return weighting, use_seed
+
+    def _cohort_average(self, what, dataset, plan_a, plan_b, two, groups, quantiles, resample, seed):
+        coef = self._effect_coef(what, _lib.COHORT_MAX_REPLICATES)
+        weighting, use_seed = self._resample(what, resample, seed)
         N = dataset.data["current_treatments"].shape[0]
         group, n_groups = self._groups(groups, N)
         prev, stat, std, mean = self._unscaled_inputs(dataset)
@@ -686,6 +691,66 @@ class SINDY:
                                          quantiles, group=group, n_groups=n_groups, weighting=weighting,
                                          seed=use_seed, method=self.integrator, drop_below=0.0, T=arm_a.size(1))
         return effect.from_cohort(out, wsum, quantiles, shift=mean, scale=std)
+
+    # ------------------------------------------------------------------ policy value
+    def policy_value(self, dataset, plans, rule=None, objective="mean", costs=None, maximize=False, groups=None,
+                     quantiles=(0.025, 0.5, 0.975), resample="paired", seed=None):
+        """What the cohort (and every subgroup) gains if every row gets its own best plan of ``plans`` instead of
+        everyone getting the best single plan, with bands from ``bootstrap_``.  ``plans``, ``objective``, ``costs``
+        and ``maximize`` are ``choose_plan``'s; ``groups``, ``resample`` and ``seed`` are ``average_effect``'s.
+        ``rule``: None (the point model's choice, ``choose_plan(...).choice``) or an int array [N] of plan indices
+        in [0, K): the fixed per-row rule that every replicate's model evaluates -- its value is free of the
+        optimism of an argmin re-derived inside the replicate, which the series "optimism" measures.  Returns an
+        ``effect.PolicyValueResult``: the series value_j, personalised, rule and best_fixed in ``choose_plan``'s
+        units ((J - mean sum_k w) / std), gain_personalised, gain_rule and optimism divided by the output's standard
+        deviation only, share_j unitless.  The shift needs one sum_k w for the whole cohort, so an [N, T]
+        ``objective`` whose rows do not all have the same sum is refused; under "mean" / "terminal" a row with no
+        active entry is excluded as a negative group id excludes it.  One launch of ``ops.policy_value``."""
+        coef = self._effect_coef("policy_value", _lib.POLICY_MAX_REPLICATES)
+        weighting, use_seed = self._resample("policy_value", resample, seed)
+        if not isinstance(plans, (list, tuple)) or not 1 <= len(plans) <= _lib.POLICY_MAX_PLANS:
+            raise ValueError(f"policy_value: plans must be a list of 1 to {_lib.POLICY_MAX_PLANS} plans")
+        K = len(plans)
+        if costs is not None and np.asarray(costs, dtype=np.float64).shape != (K,):
+            raise ValueError(f"policy_value: costs must hold one number per plan ({K})")
+        N = dataset.data["current_treatments"].shape[0]
+        rule_t = None
+        if rule is not None:
+            rl = rule.detach().cpu().numpy() if isinstance(rule, torch.Tensor) else np.asarray(rule)
+            if rl.shape != (N,) or not np.issubdtype(rl.dtype, np.integer) or (rl.size and (rl.min() < 0
+                                                                                          or rl.max() >= K)):
+                raise ValueError(f"policy_value: rule must be None or an int array [{N}] of plan indices in [0, {K})")
+            rule_t = torch.as_tensor(np.ascontiguousarray(rl.astype(np.int32)), device=self.device)
+        w = self._objective_weights(dataset, objective)
+        tot = np.broadcast_to(w.sum(axis=-1), (N,)) if w.ndim == 2 else np.full(N, w.sum())
+        g = None if groups is None else (groups.detach().cpu().numpy() if isinstance(groups, torch.Tensor)
+                                         else np.asarray(groups))
+        if isinstance(objective, str):
+            # a row with no active entry has no objective: excluded (its weights are all zero)
+            empty = ~(np.asarray(dataset.data["active_entries"][..., 0]) > 0).any(axis=1)
+            if empty.any():
+                if g is None:
+                    g = np.zeros(N, dtype=np.int64)
+                elif g.shape != (N,) or not np.issubdtype(g.dtype, np.integer):
+                    raise ValueError(f"groups: expected None or an int array [{N}] of group ids")
+                g = np.where(empty, -1, g)
+            tot = tot[~empty]
+        wtot = float(tot[0]) if tot.size else 0.0
+        if tot.size and float(np.max(tot) - np.min(tot)) > 1e-12 * max(float(np.max(np.abs(tot))), 1e-300):
+            raise ValueError("policy_value: the rows of an [N, T] objective must all have the same sum (the cohort "
+                             "value is standardised with one sum_k w): normalise every row's weights to one total")
+        group, n_groups = self._groups(g, N)
+        prev, stat, std, mean = self._unscaled_inputs(dataset)
+        arms = torch.stack([self._plan_arms(dataset, pl, f"plans[{j}]") for j, pl in enumerate(plans)]).contiguous()
+        wt = torch.as_tensor(np.ascontiguousarray(w), device=self.device)
+        cost = None
+        if costs is not None:
+            cost = torch.as_tensor(np.asarray(costs, dtype=np.float64) * std, device=self.device)
+        out, fixwin, best_fixed, rule_o, _, wsum = ops.policy_value(
+            prev[:, 0].contiguous(), stat, arms, coef, self.library, self.dt, quantiles, wt, cost=cost,
+            maximize=maximize, rule=rule_t, group=group, n_groups=n_groups, weighting=weighting, seed=use_seed,
+            method=self.integrator, drop_below=0.0, T=arms.size(2))
+        return effect.from_policy(out, fixwin, best_fixed, rule_o, wsum, quantiles, shift=mean * wtot, scale=std)
 
     # ------------------------------------------------------------------ rollout (A8)
     def _predict_device(self, dataset, tau=1):
