@@ -236,7 +236,13 @@ int32_t insite_fit_rollout_lagged_f64(const double* x, int64_t ldx, int32_t n_st
  *   seq_len  [n_patients] int32;  u [n_patients, n_statics] f64 (statics, constant over time)
  *   G_out [n_arms, F, F], b_out [n_arms, F] f64 (overwritten); deterministic (fixed-order sums).
  * insite_sindy_fit_segments_f64 adds one STLSQ fit per arm in the finalisation launch
- * (insite_sindy_fit_f64 semantics for coef_out / mask_out / iters_out). */
+ * (insite_sindy_fit_f64 semantics for coef_out / mask_out / iters_out).
+ * Workspace: insite_gram_segments_workspace_bytes, header as for insite_gram_f64.  The query does not take
+ * n_steps, on which the number of blocks (and so of partials) of a launch depends: it sizes the buffer for the
+ * most blocks any launch takes, so its result barely grows with n_patients.  Earlier builds returned less (they
+ * sized for ceil(ceil(n_patients / 64) / 4) blocks, which a cohort of long trajectories overran): a caller that
+ * kept a size from such a build gets INSITE_E_WORKSPACE and must ask again.  n_patients = 0 writes
+ * G_out = b_out = 0 (and the fit of that system). */
 size_t insite_gram_segments_workspace_bytes(int64_t n_patients, int32_t n_arms, int32_t n_terms);
 int32_t insite_gram_segments_f64(const double* x, int64_t ldx, const int8_t* arm, int64_t ld_arm, int32_t layout,
                                  int32_t n_steps, const int32_t* seq_len, const double* u, int64_t n_patients,
@@ -260,7 +266,13 @@ int32_t insite_sindy_fit_segments_f64(const double* x, int64_t ldx, const int8_t
  * model (iters 0).  Inputs as insite_gram_f64, plus
  *   global_coef [n_arms, F] f64 (device); coef_out [n_patients, n_arms, F] f64 (feeds
  *   insite_rollout_f64 with coef_row_stride = n_arms * F); mask_out [n_patients, F] int8 (may be
- *   NULL); iters_out [n_patients] int32 (may be NULL).                                          */
+ *   NULL); iters_out [n_patients] int32 (may be NULL).
+ * Workspace: insite_per_patient_workspace_bytes, exactly that many bytes suffice.  Its first 512 bytes are the
+ * discovery family's header (this call keeps no counter there, but the buffer may be shared with insite_gram_f64
+ * and the other calls that do): zero before the workspace's first use, and the call leaves them zero.  The rest
+ * (every patient's moments) needs no initialisation: the call writes every word before it reads it, so nothing is
+ * carried from an earlier call of any shape.  n_patients = 0 is a successful no-op (the outputs are not written,
+ * the workspace is not looked at). */
 size_t insite_per_patient_workspace_bytes(int64_t n_patients);
 int32_t insite_sindy_fit_per_patient_f64(const double* x, int64_t ldx, int32_t layout, int32_t n_steps,
                                          const double* u, const int8_t* arm, const int32_t* rows,
@@ -285,7 +297,8 @@ int32_t insite_sindy_fit_per_patient_f64(const double* x, int64_t ldx, int32_t l
  *     exponents;
  *   - P * n_terms <= 16, P = n_arms padded to 1, 2 or 4: three arms count as four, so 3 arms x 5 terms is
  *     refused although 15 <= 16.
- * Workspace: insite_gram_workspace_bytes. */
+ * Workspace: insite_gram_workspace_bytes.  mom_out may be NULL when n_patients = 0 (there is nothing to write: the
+ * call is then insite_gram_f64 / insite_sindy_fit_f64 on the empty cohort, G_out = b_out = 0). */
 int32_t insite_gram_moments_f64(const double* x, int64_t ldx, int32_t layout, int32_t n_steps, const double* u,
                                 const int8_t* arm, const int32_t* rows, int64_t n_patients, int32_t n_statics,
                                 int32_t n_arms, const int8_t* exps, int32_t n_terms, int32_t fd_kind, double dt,
@@ -421,7 +434,11 @@ int32_t insite_refine_arms_f64(const double* V, int64_t ld_v, int32_t T, const i
  * (fd_kind INSITE_FD_ORDER1 / INSITE_FD_SMOOTHED1) and arrays as insite_gram_segments_f64, any library with
  * state exponents <= 4 over [x, statics] (exps [n_terms][1 + n_statics], n_terms <= 64): per arm a
  *   G_out[a] = sum over arm-a segment rows of Theta^T Theta,  b_out[a] = Theta^T x_dot  (overwritten),
- * from per-patient power moments (sum x^e, e <= 8; sum x_dot x^e, e <= 4) contracted in a fixed order. */
+ * from per-patient power moments (sum x^e, e <= 8; sum x_dot x^e, e <= 4) contracted in a fixed order.
+ * Workspace: insite_gen_gram_segments_workspace_bytes, exactly that many bytes suffice.  It needs no
+ * initialisation and carries nothing between calls: every patient's record and every chunk partial is written by
+ * the call before it is read, whatever an earlier call of another shape left there.  n_patients = 0 (and a cohort
+ * without a segment) writes G_out = b_out = 0. */
 size_t insite_gen_gram_segments_workspace_bytes(int64_t n_patients, int32_t n_arms, int32_t n_terms);
 int32_t insite_gen_gram_segments_f64(const double* x, int64_t ldx, const int8_t* arm, int64_t ld_arm, int32_t layout,
                                      int32_t n_steps, const int32_t* seq_len, const double* u, int32_t n_statics,
@@ -517,7 +534,11 @@ int32_t insite_refine_rows_f64(const double* V, int64_t ld_v, int32_t T, const i
  * on the RAW x[k] (x_dot by fd_kind over the whole row), in_i(k) = bit i of step_in(p, k) (binary).
  *   x, step_in: `layout` PATIENT_MAJOR ([p * ld + k]) or TIME_MAJOR ([k * ld + p]); n_inputs <= 2
  *   exps [n_terms][1 + n_inputs + n_statics] int8 (HOST), n_terms <= 64
- *   G_out [n_groups, F, F], b_out [n_groups, F] (overwritten); deterministic fixed-order sums.   */
+ *   G_out [n_groups, F, F], b_out [n_groups, F] (overwritten); deterministic fixed-order sums.
+ * Workspace: insite_gen_gram_workspace_bytes, exactly that many bytes suffice.  It needs no initialisation and
+ * carries nothing between calls: the derivatives, every patient's record and every chunk partial are written by
+ * the call before they are read.  n_patients = 0, n_steps = 0 and a cohort without a patient of enough rows all
+ * write G_out = b_out = 0 (with n_steps = 0 no record is written and none is read). */
 size_t insite_gen_gram_workspace_bytes(int64_t n_patients, int32_t n_steps, int32_t n_groups, int32_t n_terms);
 int32_t insite_gen_gram_f64(const double* x, int64_t ldx, int32_t layout, int32_t n_steps, const double* u,
                             int32_t n_statics, const int8_t* step_in, int64_t ld_in, int32_t n_inputs,
@@ -547,7 +568,10 @@ int32_t insite_rollout_poly_f64(const double* y0, const double* u, const int8_t*
  *   last_out[0] = sum_r err[r, last_r], last_out[1] = count, where last_r is the final
  *   active entry of row r (active[r,k]=1 and active[r,k+1]=0, or k = T-1).
  * Deterministic fixed-order reduction.  pred [n_rows, ld_pred], target/active [n_rows, T].
- * Outputs f64 device arrays (overwritten). */
+ * Outputs f64 device arrays (overwritten).
+ * Workspace: insite_masked_sse_workspace_bytes, exactly that many bytes suffice.  It needs no initialisation and
+ * carries nothing between calls: every block writes its whole partial before the finalisation reads it.
+ * n_rows = 0 (and rows that are nowhere active) write zeros. */
 size_t insite_masked_sse_workspace_bytes(int64_t n_rows, int32_t T);
 int32_t insite_masked_sse_f64(const double* pred, int64_t ld_pred, double scale, double shift,
                               const double* target, const double* active, int64_t n_rows,
@@ -574,7 +598,11 @@ int32_t insite_masked_sse_f64(const double* pred, int64_t ld_pred, double scale,
  * over patients with >= 5 rows (rows may be NULL: every patient has n_steps rows).  inp_bits may be
  * NULL (library over the states only).  exps: HOST int8 [F][S + (inp_bits != NULL)], the pysindy
  * degree-2 library over those inputs (interaction_only, or full degree 2 without an input);
- * other tables return INSITE_E_UNSUPPORTED.  fd_kind: INSITE_FD_SMOOTHED4. */
+ * other tables return INSITE_E_UNSUPPORTED.  fd_kind: INSITE_FD_SMOOTHED4.
+ * Workspace: insite_gram_ms_workspace_bytes, exactly that many bytes suffice.  It needs no initialisation and
+ * carries nothing between calls: every block partial the finalisation reads is written (or, for n_patients = 0
+ * and n_steps < 5, cleared) by the call itself; those two cases and a cohort without a patient of 5 rows write
+ * G_out = B_out = 0. */
 size_t insite_gram_ms_workspace_bytes(int64_t n_patients);
 int32_t insite_gram_ms_f32(const float* x, int64_t ldx, int32_t n_steps, int32_t n_states, const uint32_t* inp_bits,
                            int64_t ld_bits, const int32_t* rows, int64_t n_patients, const int8_t* exps,

@@ -618,9 +618,11 @@ int32_t insite_gen_gram_f64(const double* x, int64_t ldx, int32_t layout, int32_
     st = launch_status();
     if (st != INSITE_OK) return st;
   }
-  const int64_t chunk = (n_patients + kGenChunks - 1) / kGenChunks > 0 ? (n_patients + kGenChunks - 1) / kGenChunks : 1;
+  // the records the launches above wrote: none when n_steps = 0 (what the workspace then holds is never read)
+  const int64_t n_rec = n_steps > 0 ? n_patients : 0;
+  const int64_t chunk = (n_rec + kGenChunks - 1) / kGenChunks > 0 ? (n_rec + kGenChunks - 1) / kGenChunks : 1;
   gen_contract_kernel<<<dim3((unsigned)((NE + kBlock - 1) / kBlock), kGenChunks), kBlock, 0, hs>>>(
-      rec, n_patients, lib, n_groups, chunk, 0, part);
+      rec, n_rec, lib, n_groups, chunk, 0, part);
   st = launch_status();
   if (st != INSITE_OK) return st;
   gen_finalize_kernel<<<(NE + kBlock - 1) / kBlock, kBlock, 0, hs>>>(part, kGenChunks, lib, n_groups, G_out, b_out);

@@ -1383,6 +1383,10 @@ stlsq_kernel(const double* __restrict__ G, const double* __restrict__ b, int64_t
 #define INSITE_SEG_PF 1
 #endif
 constexpr int kSegMaxBlocks = 8192;  // partials: kSegMaxBlocks x NARM x 64 doubles (16 MB)
+// The most blocks a ranged launch (INSITE_SEG_RANGED) takes, whatever the device reports as resident: 256 CUs x 8
+// blocks of 4 waves (the MI355X holds 4 per CU at this kernel's 4 waves per SIMD: 1024).  The ranged grid grows with
+// n_steps, which insite_gram_segments_workspace_bytes is not given, so the query sizes the partials for this bound.
+constexpr int kSegRangedBlocks = 2048;
 constexpr int kSegKC = INSITE_SEG_KC;  // steps per register chunk (loads issued ahead of the arithmetic)
 constexpr bool kSegPF = INSITE_SEG_PF != 0;  // double-buffered chunks (next chunk in flight)
 constexpr int kSegMono = INSITE_MAX_TERMS;
@@ -4495,6 +4499,7 @@ int launch_gram_seg(hipStream_t st, const double* x, int64_t xsp, int64_t xsk, c
     const int64_t units = (N + kWave - 1) / kWave * (((n_steps > 1 ? n_steps - 1 : 1) + kSegKC - 1) / kSegKC);
     int64_t r = resident_waves(kern) / kWavesPerBlock;
     if (r > (units + kWavesPerBlock - 1) / kWavesPerBlock) r = (units + kWavesPerBlock - 1) / kWavesPerBlock;
+    if (r > kSegRangedBlocks) r = kSegRangedBlocks;  // what the workspace query sized the partials for
     g = r < 1 ? 1 : (r > kSegMaxBlocks ? kSegMaxBlocks : r);
   }
   kern<<<dim3((unsigned)g), kBlock, 0, st>>>(x, xsp, xsk, arm, asp, ask, seq_len, n_steps, u, N, inv_dt, lib, part,
@@ -5048,7 +5053,9 @@ int32_t insite_gram_moments_f64(const double* x, int64_t ldx, int32_t layout, in
                                 double threshold, double alpha, int32_t max_iter, int32_t unbias, double* G_out,
                                 double* b_out, double* coef_out, int8_t* mask_out, int32_t* iters_out, double* mom_out,
                                 void* workspace, size_t workspace_bytes, void* stream) {
-  if (!mom_out || max_iter < 0 || !(threshold >= 0.0) || !(alpha >= 0.0)) return INSITE_E_INVALID_ARG;
+  // an empty cohort has no moments to write: mom_out may then be NULL (the call is insite_gram_f64 / insite_sindy_fit_f64)
+  if ((!mom_out && n_patients != 0) || max_iter < 0 || !(threshold >= 0.0) || !(alpha >= 0.0))
+    return INSITE_E_INVALID_ARG;
   const StlsqParams sp{threshold, alpha, max_iter, unbias, coef_out ? 1 : 0};
   return run_discovery(x, ldx, layout, n_steps, u, arm, rows, n_patients, n_statics, n_arms, exps, n_terms, fd_kind,
                        dt, G_out, b_out, workspace, workspace_bytes, stream, sp, coef_out, mask_out, iters_out, mom_out);
@@ -5132,9 +5139,13 @@ int32_t insite_refit_rollout_moments_f64(const double* mom, const int8_t* arm, c
 size_t insite_gram_segments_workspace_bytes(int64_t n_patients, int32_t n_arms, int32_t n_terms) {
   (void)n_terms;
   if (n_patients < 0 || n_arms < 1 || n_arms > INSITE_MAX_ARMS) return 0;
-  // block partials [grid][n_arms * nE] and <= kTailMaxGroups group partials (gram_tail), nE <= 54
+  // block partials [grid][n_arms * nE] and <= kTailMaxGroups group partials (gram_tail), nE <= 54.  The ranged launch
+  // (launch_gram_seg) takes up to kSegRangedBlocks blocks whatever n_patients is: its units are (tile, step chunk)
+  // pairs, so a short cohort with long trajectories has many more blocks than seg_grid(n_patients)
   const size_t ent = (size_t)n_arms * (INSITE_MAX_TERMS * (INSITE_MAX_TERMS + 1) / 2 + INSITE_MAX_TERMS);
-  return kGramWsHeader + ((size_t)seg_grid(n_patients) + kTailMaxGroups) * ent * sizeof(double);
+  size_t blocks = (size_t)seg_grid(n_patients);
+  if (INSITE_SEG_RANGED && blocks < (size_t)kSegRangedBlocks) blocks = kSegRangedBlocks;
+  return kGramWsHeader + (blocks + kTailMaxGroups) * ent * sizeof(double);
 }
 
 int32_t insite_gram_segments_f64(const double* x, int64_t ldx, const int8_t* arm, int64_t ld_arm, int32_t layout,
