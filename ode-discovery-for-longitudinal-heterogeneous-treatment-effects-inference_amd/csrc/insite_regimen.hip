@@ -162,13 +162,7 @@ __global__ void __launch_bounds__(kWave) regimen_choice_kernel(RgArgs ra, Affine
 
     // ---- the point model's choice and the votes ----------------------------------------------------------------
     const int pick = __builtin_amdgcn_readlane(besti[0], 0);
-    int mine = 0;
-    for (int j = 0; j < K; ++j) {
-      int cnt = 0;
-#pragma unroll
-      for (int s = 0; s < V; ++s) cnt += __builtin_popcountll(__builtin_amdgcn_ballot_w64(valid[s] && besti[s] == j));
-      mine = lane == j ? cnt : mine;
-    }
+    const int mine = ef_vote_counts<V>(valid, besti, K, lane);
     if (lane == 0) ra.choice[p] = pick;
     if (lane < K) ra.win[p * K + lane] = (double)mine / (double)n;
 

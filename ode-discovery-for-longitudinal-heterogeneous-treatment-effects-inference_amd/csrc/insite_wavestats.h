@@ -1,7 +1,7 @@
 // insite_wavestats.h — the one definition of the order statistics and moments one wave takes over the bootstrap
 // replicates it holds in registers (lane l, slot s = replicate s 64 + l; V = R_pad / 64 slots per lane): the lane
-// exchanges, the fixed-order wave sums, the in-register bitonic sort, the read of a sorted rank and, built on them,
-// ef_series_stats: the point value, moments, quantiles and NaN rule of include/insite_effect.h.  effect_bands_kernel
+// exchanges, the fixed-order wave sums, the in-register bitonic sort, the read of a sorted rank, the vote count and,
+// built on them, ef_series_stats: the point value, moments, quantiles and NaN rule of include/insite_effect.h.  effect_bands_kernel
 // (insite_effect.hip) and regimen_choice_kernel (insite_regimen.hip, §9j) both call ef_series_stats
 // and differ only in the stride of the staging writes, so the regimen statistics are the effect bands' by
 // construction.  The quantile interpolation is insite_affine.h's quantile_interp, shared with the cohort finalize.
@@ -173,6 +173,20 @@ __device__ __forceinline__ double ef_rank_value(const double (&key)[V], int i) {
     for (int s = 0; s < (V >> (b + 1)); ++s) x[s] = odd ? x[2 * s + 1] : x[2 * s];
   }
   return readlane_f64(x[0], i >> LV);
+}
+
+// The votes of the valid slots (regimen_choice_kernel, feedback_rules_kernel): lane j < K returns the number of valid
+// slots of the wave whose best[s] is j (an exact count: ballot + popcount per candidate), the other lanes 0.
+template <int V>
+__device__ __forceinline__ int ef_vote_counts(const bool (&valid)[V], const int (&best)[V], int K, int lane) {
+  int mine = 0;
+  for (int j = 0; j < K; ++j) {
+    int cnt = 0;
+#pragma unroll
+    for (int s = 0; s < V; ++s) cnt += __builtin_popcountll(__builtin_amdgcn_ballot_w64(valid[s] && best[s] == j));
+    mine = lane == j ? cnt : mine;
+  }
+  return mine;
 }
 
 // The statistics of NB series over the replicates 1..R-1 = the valid slots (insite_effect.h: the point model's value,

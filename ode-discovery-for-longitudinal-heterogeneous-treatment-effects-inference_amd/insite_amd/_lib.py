@@ -40,6 +40,9 @@ REGIMEN_ABI_VERSION, REGIMEN_MAX_REPLICATES, REGIMEN_MAX_QUANTILES, REGIMEN_MAX_
 REGIMEN_MINIMIZE, REGIMEN_MAXIMIZE = 1, -1
 # include/insite_policy.h
 POLICY_ABI_VERSION, POLICY_MAX_REPLICATES, POLICY_MAX_PLANS, POLICY_MAX_GROUPS, POLICY_MAX_QUANTILES = 1, 4096, 16, 64, 16
+# include/insite_feedback.h
+FEEDBACK_ABI_VERSION, FEEDBACK_MAX_REPLICATES, FEEDBACK_MAX_QUANTILES, FEEDBACK_MAX_RULES = 1, 512, 16, 16
+FEEDBACK_MINIMIZE, FEEDBACK_MAXIMIZE = 1, -1
 METHOD_EULER, METHOD_RK4 = 0, 1
 LAYOUT_PATIENT_MAJOR, LAYOUT_TIME_MAJOR, LAYOUT_TIME_MAJOR_BITS, LAYOUT_PATIENT_MAJOR_BITS = 0, 1, 2, 3
 MAX_TERMS, MAX_STATICS, MAX_ARMS, MAX_STATE_DEGREE = 9, 3, 4, 1
@@ -152,6 +155,13 @@ POLICY_EXPORTS = (
     "insite_policy_sums_f64",
     "insite_policy_finalize_f64",
     "insite_policy_value_f64",
+)
+
+# the extension header include/insite_feedback.h (same shared library, its own ABI version).  Not named *_EXPORTS:
+# tests/test_workspace_matrix.py pins the set of names with that ending, and this entry point takes no workspace
+FEEDBACK_SYMBOLS = (
+    "insite_feedback_abi_version",
+    "insite_feedback_rules_f64",
 )
 
 
@@ -322,6 +332,11 @@ _SIGNATURES = {
     "insite_policy_value_f64": (_c_i32, [_vp, _vp, _vp, _c_i32, _c_i64, _c_i64, _vp, _c_i64, _vp, _c_i32, _vp, _vp, _c_i32, _c_i64,
                                         _c_i32, _c_i32, _c_i32, _c_f64, _c_i32, _c_i32, _c_f64, _c_i32, _vp, _c_i32,
                                         _c_i32, ctypes.c_uint32, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_i32, _vp, _c_i64, _vp, _vp, _vp, _c_size, _vp]),
+    # insite_feedback.h
+    "insite_feedback_abi_version": (_c_i32, []),
+    "insite_feedback_rules_f64": (_c_i32, [_vp, _vp, _vp, _c_i64, _vp, _c_i32, _vp, _c_i64, _vp, _vp, _c_i32, _vp, _vp,
+                                           _c_i32, _c_i64, _c_i32, _c_i32, _c_i32, _c_f64, _c_i32, _c_i32, _c_f64,
+                                           _c_i32, _vp, _c_i32, _vp, _vp, _vp, _c_i64, _vp, _c_i64, _vp]),
 }
 
 # (getter, the version these bindings were written for, the label of the mismatch message)
@@ -334,6 +349,7 @@ _ABI_VERSIONS = (
     ("insite_cohort_abi_version", COHORT_ABI_VERSION, "cohort "),
     ("insite_regimen_abi_version", REGIMEN_ABI_VERSION, "regimen "),
     ("insite_policy_abi_version", POLICY_ABI_VERSION, "policy "),
+    ("insite_feedback_abi_version", FEEDBACK_ABI_VERSION, "feedback "),
 )
 
 

@@ -123,6 +123,66 @@ def from_regimen(choice: torch.Tensor, win: torch.Tensor, out: torch.Tensor, q, 
                                quantiles=res[:, 3:], q=tuple(float(v) for v in q))
 
 
+FEEDBACK_SERIES = ("value", "regret", "exposure")
+
+
+@dataclasses.dataclass
+class ThresholdRule:
+    """A closed-loop treatment rule on the predicted state (include/insite_feedback.h): every
+    ``every``-th step, switch to ``arm_on`` when the state before the step is >= ``on`` and back to ``arm_off`` when
+    it falls below ``off`` (``off`` None: ``off = on``, the memoryless rule; ``off < on``: hysteresis).  ``on`` and
+    ``off`` are numbers or arrays [N] (one threshold per row), in the units of ``get_predictions``.  ``start_on``:
+    the rule's flag before the first step (it matters only under hysteresis)."""
+    on: object
+    off: object = None
+    arm_on: int = 1
+    arm_off: int = 0
+    every: int = 1
+    start_on: bool = False
+
+
+@dataclasses.dataclass
+class FeedbackResult:
+    """K closed-loop rules per row of ``ops.feedback_rules`` (include/insite_feedback.h).  ``choice``
+    int32 [N]: the point model's best rule (-1: it has a NaN objective); ``win`` [N, K]: the share of the replicates
+    1..R-1 in which rule j is the best.  ``series``: ("value", "regret", "exposure").  ``point``, ``mean``, ``std``
+    [3, N, K]: per rule the objective, the regret against the replicate's own best rule and the exposure (the number
+    of steps spent on), as the point model's value and the mean / standard deviation (n - 1 divisor) over the
+    replicates 1..R-1; ``quantiles`` [3, Q, N, K] in the order of ``q``.  ``schedule`` int8 [N, K, T] or None: the arm
+    the point model applies at every step under every rule.  ``result["exposure"]`` gives one series as a dict."""
+    choice: torch.Tensor
+    win: torch.Tensor
+    point: torch.Tensor
+    mean: torch.Tensor
+    std: torch.Tensor
+    quantiles: torch.Tensor
+    q: tuple
+    schedule: torch.Tensor | None = None
+    series: tuple = FEEDBACK_SERIES
+
+    def __getitem__(self, name: str) -> dict:
+        i = self.series.index(name)
+        return {"point": self.point[i], "mean": self.mean[i], "std": self.std[i], "quantiles": self.quantiles[i]}
+
+
+def from_feedback(choice: torch.Tensor, win: torch.Tensor, out: torch.Tensor, q, schedule=None, shift=0.0,
+                  scale: float = 1.0) -> FeedbackResult:
+    """``ops.feedback_rules``' (choice, win, out [N, K, 3, 3 + Q], sched) as a ``FeedbackResult`` in the scale
+    (x - shift) / scale, by ``from_regimen``'s rule: the locations of the value series are shifted and divided, its
+    standard deviation and every statistic of the regret are divided only; the exposure (a count of steps) is left
+    as it is.  ``shift``: a number or a tensor [N]."""
+    if out.dim() != 4 or out.size(2) != 3 or out.size(3) != 3 + len(q):
+        raise ValueError("out must be [N, K, 3, 3 + Q]")
+    o = out.permute(2, 3, 0, 1)                     # [3, 3 + Q, N, K]
+    res = o.clone()
+    res[:2] = o[:2] / scale
+    loc = [0, 1] + list(range(3, o.size(1)))        # point, mean and quantiles
+    sh = shift[:, None] if isinstance(shift, torch.Tensor) else shift
+    res[0, loc] = (o[0, loc] - sh) / scale
+    return FeedbackResult(choice=choice, win=win, point=res[:, 0], mean=res[:, 1], std=res[:, 2],
+                          quantiles=res[:, 3:], q=tuple(float(v) for v in q), schedule=schedule)
+
+
 def policy_series(n_plans: int) -> tuple:
     """The names of the 2 K + 6 series of ``ops.policy_value`` in the order of include/insite_policy.h."""
     K = int(n_plans)

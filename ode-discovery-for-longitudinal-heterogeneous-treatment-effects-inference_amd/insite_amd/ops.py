@@ -1097,6 +1097,119 @@ def plan_regimen_choice(y0, u, plans, coef, lib, dt, quantiles, weights, cost=No
     return Plan(name, args, dev, outs, keep)
 
 
+def _prep_feedback_rules(y0, u, theta, rules, coef, lib, dt, quantiles, weights, cost, arm_cost, maximize, method,
+                         substeps, drop_below, T, out, sched):
+    """Validate the inputs of the closed-loop rules and pack the C arguments (insite_feedback.h)."""
+    _lib.load()
+    rl = np.ascontiguousarray(np.asarray(rules, dtype=np.int64).reshape(-1, 4) if np.size(rules) else
+                              np.zeros((0, 4), dtype=np.int64))
+    K = rl.shape[0]
+    if not 1 <= K <= _lib.FEEDBACK_MAX_RULES:
+        raise ValueError(f"between 1 and {_lib.FEEDBACK_MAX_RULES} rules (arm_on, arm_off, period, start_on) expected, "
+                         f"got {K}")
+    _dev("y0", y0, torch.float64, 1)
+    N = y0.numel()
+    if not isinstance(weights, torch.Tensor) or not weights.is_cuda or weights.dim() not in (1, 2):
+        _dev("weights", weights, torch.float64)
+        raise ValueError("weights must be f64 [T] (shared by the rows) or [N, >=T]")
+    _dev("weights", weights, torch.float64, weights.dim())
+    T = weights.size(-1) if T is None else int(T)
+    if T < 1 or weights.size(-1) < T or (weights.dim() == 2 and weights.size(0) != N):
+        raise ValueError("T must be >= 1 and weights f64 [T] (shared by the rows) or [N, >=T]")
+    ld_w = 0 if weights.dim() == 1 else (weights.stride(0) if N > 1 else T)
+    _dev("theta", theta, torch.float64, 2)
+    if theta.size(0) == N and theta.size(1) >= 2 * K:      # per-row thresholds (N = K = 1: the same numbers either way)
+        ld_theta = theta.stride(0) if N > 1 else 2 * K
+    elif tuple(theta.shape) == (K, 2) and theta.is_contiguous():
+        ld_theta = 0
+    else:
+        raise ValueError("theta must be f64, a contiguous [K, 2] table (shared by the rows) or [N, >=2K]")
+    if cost is not None:
+        _dev("cost", cost, torch.float64, 1)
+        if cost.numel() != K or not cost.is_contiguous():
+            raise ValueError("cost must be a contiguous f64 [K] tensor")
+    R, A = _check_statics_coef(u, coef, lib, N, _lib.FEEDBACK_MAX_REPLICATES)
+    if (rl[:, :2] < 0).any() or (rl[:, :2] >= A).any() or (rl[:, 2] < 1).any() or (rl[:, 2] > 2**31 - 1).any() \
+            or ((rl[:, 3] != 0) & (rl[:, 3] != 1)).any():
+        raise ValueError(f"rules: arm_on and arm_off must lie in [0, {A}), period must be >= 1, start_on 0 or 1")
+    rl = np.ascontiguousarray(rl.astype(np.int32))
+    ac = None
+    if arm_cost is not None:
+        ac = np.ascontiguousarray(np.asarray(arm_cost, dtype=np.float64))
+        if ac.shape != (A,):
+            raise ValueError(f"arm_cost must hold one number per arm ({A})")
+    F = lib.n_terms
+    q = _quantiles(quantiles, _lib.FEEDBACK_MAX_QUANTILES)
+    m, sub = _method(method, substeps)
+    dev = y0.device
+    NS = 3 + q.size
+    shape = (N, K, 3, NS)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=dev)
+        ld_out = K * 3 * NS
+    else:
+        _dev("out", out, torch.float64, 4)
+        ld_out = out.stride(0) if N > 1 else K * 3 * NS
+        if (tuple(out.shape) != shape or ld_out < K * 3 * NS
+                or (N > 0 and (out.stride(3) != 1 or out.stride(2) != NS or (K > 1 and out.stride(1) != 3 * NS)))):
+            raise ValueError(f"out must be {shape}, every row's [K, 3, 3 + Q] block dense (rows may be padded)")
+    ld_sched = 0
+    if sched is None or sched is False:
+        sched = None
+    elif sched is True:
+        sched = torch.empty((N, K, T), dtype=torch.int8, device=dev)
+        ld_sched = K * T
+    else:
+        if not isinstance(sched, torch.Tensor) or not sched.is_cuda or sched.dtype != torch.int8 or sched.dim() != 3:
+            raise ValueError("sched: expected None, True or an int8 device tensor [N, K, T]")
+        ld_sched = sched.stride(0) if N > 1 else K * T
+        if (tuple(sched.shape) != (N, K, T) or ld_sched < K * T
+                or (N > 0 and ((T > 1 and sched.stride(2) != 1) or (K > 1 and sched.stride(1) != T)))):
+            raise ValueError(f"sched must be {(N, K, T)}, every row's [K, T] block dense (rows may be padded)")
+    choice = torch.empty(N, dtype=torch.int32, device=dev)
+    win = torch.empty((N, K), dtype=torch.float64, device=dev)
+    tab = lib.ctypes_table()
+    args = (_p(y0), _p(u) if lib.n_statics else ctypes.c_void_p(0), _p(theta), ld_theta,
+            rl.ctypes.data_as(ctypes.c_void_p), K, _p(weights), ld_w, _p(cost),
+            ac.ctypes.data_as(ctypes.c_void_p) if ac is not None else ctypes.c_void_p(0),
+            _lib.FEEDBACK_MAXIMIZE if maximize else _lib.FEEDBACK_MINIMIZE, _p(coef),
+            tab.ctypes.data_as(ctypes.c_void_p), F, N, T, lib.n_statics, A, float(dt), m, sub, float(drop_below), R,
+            q.ctypes.data_as(ctypes.c_void_p), q.size, _p(choice), _p(win), _p(out), ld_out, _p(sched), ld_sched)
+    return ("insite_feedback_rules_f64", args, dev, (choice, win, out, sched),
+            (y0, u, theta, rl, weights, cost, ac, coef, tab, q, choice, win, out, sched))
+
+
+def feedback_rules(y0: torch.Tensor, u: torch.Tensor, theta: torch.Tensor, rules, coef: torch.Tensor,
+                   lib: PolyLibrary, dt: float, quantiles, weights: torch.Tensor, cost: torch.Tensor | None = None,
+                   arm_cost=None, maximize: bool = False, method: str = "euler5", substeps: int | None = None,
+                   drop_below: float = 1e-3, T: int | None = None, out: torch.Tensor | None = None, sched=None):
+    """K closed-loop treatment rules per row, over a bootstrap ensemble (insite_feedback_rules_f64).
+
+    Rule j is the host row ``rules[j]`` = (arm_on, arm_off, period, start_on) with the device thresholds
+    ``theta[..., 2 j]`` (switch on) and ``theta[..., 2 j + 1]`` (stay on): at every ``period``-th step the state before
+    the interval is compared with the threshold the rule's current flag selects, inside each replicate, and the
+    interval runs under arm_on or arm_off.  y0 [N] f64, u [N, U] f64, theta f64 [K, 2] (shared by the rows) or
+    [N, >=2K], coef [R, A, F] (replicate 0 the point model), weights f64 [T] or [N, >=T], cost f64 [K] (device) or
+    None, arm_cost: A numbers on the host or None (a cost per step spent under each arm).  The objective is
+    J = cost[j] + sum_k (w[p, k] y[k] + arm_cost[arm_k]); the best rule is taken inside each replicate as
+    ``regimen_choice`` takes the best plan.  Returns (choice int32 [N], win f64 [N, K], out f64 [N, K, 3, 3 + Q]: per
+    rule the objective, the regret and the exposure (the number of steps spent on), each as point value, mean,
+    standard deviation (ddof 1) and the ``quantiles`` over the replicates 1..R-1; sched).  ``sched``: None (not
+    written, returned as None), True (allocated) or an int8 tensor [N, K, T] (rows may be padded): the arm the point
+    model applies at every step under every rule, ready to be passed on as per-row plans."""
+    return _run(_prep_feedback_rules(y0, u, theta, rules, coef, lib, dt, quantiles, weights, cost, arm_cost, maximize,
+                                     method, substeps, drop_below, T, out, sched))
+
+
+def plan_feedback_rules(y0, u, theta, rules, coef, lib, dt, quantiles, weights, cost=None, arm_cost=None,
+                        maximize=False, method="euler5", substeps=None, drop_below=1e-3, T=None, out=None,
+                        sched=None) -> Plan:
+    """``feedback_rules`` as a prepared launch; ``plan.out`` = (choice, win, out, sched)."""
+    name, args, dev, outs, keep = _prep_feedback_rules(y0, u, theta, rules, coef, lib, dt, quantiles, weights, cost,
+                                                       arm_cost, maximize, method, substeps, drop_below, T, out, sched)
+    return Plan(name, args, dev, outs, keep)
+
+
 COHORT_WEIGHTINGS = {"none": _lib.COHORT_WEIGHT_NONE, "poisson": _lib.COHORT_WEIGHT_POISSON}
 
 

@@ -623,6 +623,57 @@ class SINDY:
         return effect.from_regimen(choice, win, out, quantiles, shift=shift if w.dim() == 2 else float(shift),
                                    scale=std)
 
+    # ------------------------------------------------------------------ closed-loop rules
+    def evaluate_rules(self, dataset, rules, objective="mean", costs=None, arm_costs=None, maximize=False,
+                       quantiles=(0.025, 0.5, 0.975), schedule=False):
+        """How each of the closed-loop ``rules`` does for every row of ``dataset``, and how sure the bootstrap ensemble
+        is of it.  ``rules``: a list of 1..16 ``effect.ThresholdRule`` -- "treat (arm_on) while the predicted state is
+        at or above a threshold", decided every ``every`` steps on the state the model itself predicts, so every
+        bootstrap replicate follows its own treatment sequence.  Thresholds are in the units of ``get_predictions``
+        (numbers, or one per row).  ``objective``, ``costs`` (one per rule) and ``maximize`` are ``choose_plan``'s;
+        ``arm_costs``: one number per arm in the same units, charged for every step spent under that arm (the
+        exposure of a rule is not known in advance, so it cannot be part of ``costs``).  Returns an
+        ``effect.FeedbackResult``: ``choice`` (the point model's rule), ``win`` [N, K] and per rule the series "value"
+        and "regret" (``choose_plan``'s units) and "exposure" (the number of steps spent on arm_on, with its own band);
+        with ``schedule`` also the arms the point model applies, int8 [N, K, T], which ``treatment_effect`` and
+        ``choose_plan`` take as plans.  One launch of ``ops.feedback_rules``."""
+        coef = self._effect_coef("evaluate_rules", _lib.FEEDBACK_MAX_REPLICATES)
+        if (not isinstance(rules, (list, tuple)) or not 1 <= len(rules) <= _lib.FEEDBACK_MAX_RULES
+                or not all(isinstance(r, effect.ThresholdRule) for r in rules)):
+            raise ValueError(f"evaluate_rules: rules must be a list of 1 to {_lib.FEEDBACK_MAX_RULES} "
+                             "effect.ThresholdRule")
+        K = len(rules)
+        if costs is not None and np.asarray(costs, dtype=np.float64).shape != (K,):
+            raise ValueError(f"evaluate_rules: costs must hold one number per rule ({K})")
+        A = self.dim_treatments
+        if arm_costs is not None and np.asarray(arm_costs, dtype=np.float64).shape != (A,):
+            raise ValueError(f"evaluate_rules: arm_costs must hold one number per arm ({A})")
+        N = dataset.data["current_treatments"].shape[0]
+        table, th = [], np.empty((N, 2 * K))
+        for j, r in enumerate(rules):
+            if not (0 <= int(r.arm_on) < A and 0 <= int(r.arm_off) < A) or int(r.every) < 1:
+                raise ValueError(f"evaluate_rules: rules[{j}]: arms must lie in [0, {A}) and every must be >= 1")
+            table.append((int(r.arm_on), int(r.arm_off), int(r.every), 1 if r.start_on else 0))
+            for c, v in ((2 * j, r.on), (2 * j + 1, r.on if r.off is None else r.off)):
+                v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, dtype=np.float64)
+                if v.shape not in ((), (N,)):
+                    raise ValueError(f"evaluate_rules: rules[{j}]: a threshold is a number or an array [{N}]")
+                th[:, c] = v
+        prev, stat, std, mean = self._unscaled_inputs(dataset)
+        theta = torch.as_tensor(th * std + mean, device=self.device)
+        w = torch.as_tensor(np.ascontiguousarray(self._objective_weights(dataset, objective)), device=self.device)
+        cost = None
+        if costs is not None:
+            cost = torch.as_tensor(np.asarray(costs, dtype=np.float64) * std, device=self.device)
+        ac = None if arm_costs is None else np.asarray(arm_costs, dtype=np.float64) * std
+        choice, win, out, sched = ops.feedback_rules(prev[:, 0].contiguous(), stat, theta, table, coef, self.library,
+                                                     self.dt, quantiles, w, cost=cost, arm_cost=ac, maximize=maximize,
+                                                     method=self.integrator, drop_below=0.0, T=w.size(-1),
+                                                     sched=True if schedule else None)
+        shift = mean * w.sum(dim=-1)                # a number (shared weights) or [N]
+        return effect.from_feedback(choice, win, out, quantiles, schedule=sched,
+                                    shift=shift if w.dim() == 2 else float(shift), scale=std)
+
     # ------------------------------------------------------------------ cohort averages (DESIGN.md §9i)
     def _groups(self, groups, N):
         """``groups`` None (one group) or int ids [N] (negative: the row is excluded) -> (int32 device tensor or None,
