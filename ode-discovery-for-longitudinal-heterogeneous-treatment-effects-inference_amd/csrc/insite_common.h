@@ -96,7 +96,17 @@ struct GramW {
   double sg0, sg1, sg2;  // savgol interior: sg0*x[k] + sg1*(x[k-1]+x[k+1]) + sg2*(x[k-2]+x[k+2])
   double fd1, fd2;       // FD4 interior:   fd1*(v[k+1]-v[k-1]) + fd2*(v[k+2]-v[k-2])
   double inv_dt;
+  // FD4 interior of savgol interior on the raw samples: d[k] = sum_j cj*(x[k+j]-x[k-j]), j = 1..4 (the
+  // convolution of the two rows above; cj*dt = (148, 79, -36, 3)/420)
+  double c1, c2, c3, c4;
 };
+// The composite taps from the weights they are made of (host side, after sg* / fd* are set).
+inline void gram_w_composite(GramW& w) {
+  w.c1 = w.fd1 * w.sg0 + w.fd2 * w.sg1 - w.fd1 * w.sg2;
+  w.c2 = w.fd1 * w.sg1 + w.fd2 * w.sg0;
+  w.c3 = w.fd1 * w.sg2 + w.fd2 * w.sg1;
+  w.c4 = w.fd2 * w.sg2;
+}
 
 __device__ __forceinline__ double sg_int(const GramW& w, double a, double b, double c, double d, double e) {
   return w.sg0 * c + w.sg1 * (b + d) + w.sg2 * (a + e);

@@ -113,7 +113,7 @@ __device__ __forceinline__ int col_ex(const LibDesc& lib, int j) { return (lib.u
 #ifndef INSITE_PF
 #define INSITE_PF 1
 #endif
-constexpr int kGT = INSITE_GT;     // time tile in steps: a multiple of the register ring length (8)
+constexpr int kGT = INSITE_GT;     // time tile in steps: >= 8, the first tile holds the head samples x[0..7]
 constexpr int kGStride = kGT + 1;  // LDS row stride in doubles (odd -> lane-per-row reads conflict free)
 // per-wave LDS slot: 64 rows of max(kGStride, 17) doubles -- also the MFMA contraction's staging rows
 // (32 x 23) and the scalar path's 64 x kPsStride rows
@@ -180,6 +180,32 @@ __device__ __forceinline__ void tele_lo(const GramW& w, double vm2, double vm1, 
                                         double& sdx) {  // v_{a-2}, v_{a-1}, v_a, v_{a+1}
   sd = w.fd1 * (v0 + vm1) + w.fd2 * ((v1 + v0) + (vm1 + vm2));
   sdx = w.fd1 * (vm1 * v0) + w.fd2 * (vm2 * v0 + vm1 * v1);
+}
+// The smoothed instance telescopes the same way: savgol (symmetric) then FD4 (antisymmetric) is the 9-tap
+// antisymmetric filter d_k = sum_{j=1..4} c_j (x_{k+j} - x_{k-j}) on the raw samples, the sequence the library is
+// evaluated on.  For the interior rows k = a..b (a = 4, b = L - 5: every stencil the interior one)
+//   sum d_k     = sum_j c_j [ sum_{i=b-j+1..b+j} x_i          - sum_{i=a-j..a+j-1} x_i ]
+//   sum d_k x_k = sum_j c_j [ sum_{k=b-j+1..b} x_k x_{k+j}    - sum_{k=a-j..a-1} x_k x_{k+j} ]
+// Either bracket term reads the eight samples around its end, v[0..7] = x[m-3..m+4] with m = b (hi) or
+// m = a - 1 (lo), through the same expression: hi on x[L-8..L-1], lo on x[0..7].
+__device__ __forceinline__ void tele9_end(const GramW& w, const double (&v)[8], double& sd, double& sdx) {
+  const double s1 = v[3] + v[4];
+  const double s2 = s1 + (v[2] + v[5]);
+  const double s3 = s2 + (v[1] + v[6]);
+  const double s4 = s3 + (v[0] + v[7]);
+  sd = (w.c1 * s1 + w.c2 * s2) + (w.c3 * s3 + w.c4 * s4);
+  sdx = (w.c1 * (v[3] * v[4]) + w.c2 * (v[2] * v[4] + v[3] * v[5])) +
+        (w.c3 * (v[1] * v[4] + v[2] * v[5] + v[3] * v[6]) + w.c4 * ((v[0] * v[4] + v[1] * v[5]) + (v[2] * v[6] + v[3] * v[7])));
+}
+__device__ __forceinline__ void tele9_hi(const GramW& w, const double (&xe)[8], double& sd, double& sdx) {  // x[L-8..L-1]
+  tele9_end(w, xe, sd, sdx);
+}
+__device__ __forceinline__ void tele9_lo(const GramW& w, const double (&xh)[8], double& sd, double& sdx) {  // x[0..7]
+  tele9_end(w, xh, sd, sdx);
+}
+__device__ __forceinline__ void add_drow(double xk, double dk, double& Sd, double& Sdx) {
+  Sd += dk;
+  Sdx = fma(dk, xk, Sdx);
 }
 
 // In-launch fixed-order reduction of the gram partials (the split-K hand-off of the MI355X HIP guide,
@@ -560,8 +586,8 @@ __device__ __forceinline__ void gram_body(const int vblk, const int vgrid, doubl
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);  // wave-uniform (SGPR)
   double* xt = smem + wid * (kWave * kGSlot);
   constexpr int kMinMain = SMOOTH ? 8 : 5;  // shorter (5..7, smoothed) rows take small_trajectory
-  constexpr int kWarm = SMOOTH ? 8 : 4;     // warm-up steps of a segment's first tile
-  constexpr int kLag = SMOOTH ? 4 : 2;      // body row kd = t - kLag
+  constexpr int kEdge = SMOOTH ? 4 : 2;     // head rows 0..kEdge-1 and tail rows L-kEdge..L-1 (positional stencils)
+  static_assert(kGT >= kMinMain, "the first tile holds the head samples x[0 .. kMinMain)");
   constexpr int LPR = kGT / VEC;            // lanes per row segment
   constexpr int RPI = kWave / LPR;          // rows per wave instruction
   constexpr int NLD = kWave / RPI;          // load instructions per tile
@@ -743,7 +769,7 @@ __device__ __forceinline__ void gram_body(const int vblk, const int vgrid, doubl
     // range is clipped at the stored steps, not at this wave's longest row, which is not known yet)
     const int s0 = pc.s0;       // first step owned by this piece
     const bool first = s0 == 0;  // the piece holding the head rows (and the row count) of its tile
-    const int tb = first ? 0 : s0 - kWarm;
+    const int tb = s0;           // a piece streams its own steps only (no warm-up re-read)
     const int tm_valid = (int)(N - p0 < kWave ? N - p0 : kWave);
     const unsigned tm_off = p < N ? (unsigned)lane * 8u : kOOB;
     auto tm_load = [&](TmTile& v, int t0, int lim) { tm_load_for(v, t0, lim, p0, tm_valid, tm_off); };
@@ -780,8 +806,6 @@ __device__ __forceinline__ void gram_body(const int vblk, const int vgrid, doubl
     INSITE_TSTAMP(blockIdx.x * kWavesPerBlock + wid, 1);
     const int e = min(Lm, pc.sE);            // per-lane end of owned steps
     const int Lmin = wave_min_i(e);
-    const int bstart = max(2 * kLag, s0);    // first body step of the segment
-    const bool has_body = e > bstart;        // at least one body row owned
     double Sx = 0.0, Sxx = 0.0, Sd = 0.0, Sdx = 0.0;
 
     if (s0 < Lmax) {
@@ -820,18 +844,25 @@ __device__ __forceinline__ void gram_body(const int vblk, const int vgrid, doubl
         wave_lds_sync();
       };
 
-      double xr[8], sr[8];  // rings: xr[i & 7] = x[tb + i];  sr[k & 7] = xs[tb + k]
-#pragma unroll
-      for (int j = 0; j < 8; ++j) xr[j] = sr[j] = 0.0;
-      double loSd = 0.0, loSdx = 0.0;  // telescoped a-side terms
-      // b-side / tail samples x[e-8 .. e-1] (x[e-5 .. e-1] unsmoothed), loaded during the last tile
-      const bool tail = Lm > 0 && e == Lm && Lm - 1 >= s0;  // this segment holds step L-1
-      const bool need_end = has_body || tail;
-      constexpr int NQ = SMOOTH ? 8 : 5;
+      // Row ownership.  A piece owns the rows of its own steps: row t of a lane enters Sx / Sxx in the piece with
+      // s0 <= t < e, so over the pieces of a tile every row 0..L-1 of every lane is counted exactly once.  The
+      // derivative moments need no per-row work: the body rows kEdge..L-1-kEdge telescope (tele_lo / tele_hi,
+      // tele9_*) to -lo on x[0..NQ-1], added by the piece with `first`, and +hi on x[L-NQ..L-1], added by the
+      // lane's `tail` piece, next to the head / tail rows' positional stencils on the same samples -- one of each
+      // per lane whatever the cuts and the lanes' row counts are.  A piece that is neither only streams.
+      const bool body = Lm > 2 * kEdge;  // the lane has body rows (smoothed L = 8: head and tail rows only)
+      double loSd = 0.0, loSdx = 0.0;    // telescoped a-side terms (first piece)
+      // b-side / tail samples x[L-8 .. L-1] (x[L-5 .. L-1] unsmoothed), loaded during the last tile
+      const bool tail = Lm > 0 && e == Lm && Lm - 1 >= s0;  // this piece holds the lane's step L-1
+      const bool need_end = tail;
+      const bool any_tail = __builtin_amdgcn_ballot_w64(tail) != 0;  // uniform
+      constexpr int NQ = kMinMain;
       double qe[NQ];
+#pragma unroll
+      for (int j = 0; j < NQ; ++j) qe[j] = 0.0;
       bool tail_issued = false;
       auto issue_tail = [&]() {
-        if (tail_issued) return;
+        if (tail_issued || !any_tail) return;
         tail_issued = true;
         // valid either way: e >= NQ when need_end, and the patient-major ldx >= L >= NQ
         const int64_t pc = p < N ? p : N - 1;
@@ -869,59 +900,7 @@ __device__ __forceinline__ void gram_body(const int vblk, const int vgrid, doubl
           if (tb + kGT >= s1) issue_tail();
         }
       }
-      {
-        const bool masked = tb + kGT > Lmin;
-#pragma unroll
-        for (int i = 0; i < kGT; ++i) {
-          if constexpr (TM) xr[i & 7] = sample(vr[0], i);
-          else xr[i & 7] = sample(vA, i);
-          const int t = tb + i;
-          if constexpr (SMOOTH) {
-            if (i >= 4) sr[(i - 2) & 7] = sg_int(w, xr[(i - 4) & 7], xr[(i - 3) & 7], xr[(i - 2) & 7], xr[(i - 1) & 7], xr[i & 7]);
-            if (i == 7) {
-              if (first) {  // head rows kd = 0..3 from x[0..7], xs[2..5]
-                const double xs0 = sg_pos0(xr[0], xr[1], xr[2], xr[3], xr[4]);
-                const double xs1 = sg_pos1(xr[0], xr[1], xr[2], xr[3], xr[4]);
-                const double d0 = fd_pos0(xs0, xs1, sr[2], sr[3], sr[4]) * w.inv_dt;
-                const double d1 = fd_pos1(xs0, xs1, sr[2], sr[3], sr[4]) * w.inv_dt;
-                const double d2 = fd_int(w, xs0, xs1, sr[3], sr[4]);
-                const double d3 = fd_int(w, xs1, sr[2], sr[4], sr[5]);
-                const bool on = Lm > 0;
-                add_row(on ? xr[0] : 0.0, on ? d0 : 0.0, Sx, Sxx, Sd, Sdx);
-                add_row(on ? xr[1] : 0.0, on ? d1 : 0.0, Sx, Sxx, Sd, Sdx);
-                add_row(on ? xr[2] : 0.0, on ? d2 : 0.0, Sx, Sxx, Sd, Sdx);
-                add_row(on ? xr[3] : 0.0, on ? d3 : 0.0, Sx, Sxx, Sd, Sdx);
-              }
-            }
-            if (i >= 8) {  // body row kd = t - 4: raw x[kd], x_dot from xs[kd-2 .. kd+2]
-              double xk = xr[(i - 4) & 7];
-              double dk = fd_int(w, sr[(i - 6) & 7], sr[(i - 5) & 7], sr[(i - 3) & 7], sr[(i - 2) & 7]);
-              if (masked) {
-                xk = (t < e) ? xk : 0.0;
-                dk = (t < e) ? dk : 0.0;
-              }
-              add_row(xk, dk, Sx, Sxx, Sd, Sdx);
-            }
-          } else {
-            if (i == 3) tele_lo(w, xr[0], xr[1], xr[2], xr[3], loSd, loSdx);  // x[a-2..a+1], a = tb + 2
-            if (i == 4 && first) {  // head rows kd = 0, 1 from x[0..4]
-              const double d0 = fd_pos0(xr[0], xr[1], xr[2], xr[3], xr[4]) * w.inv_dt;
-              const double d1 = fd_pos1(xr[0], xr[1], xr[2], xr[3], xr[4]) * w.inv_dt;
-              const bool on = Lm > 0;
-              add_row(on ? xr[0] : 0.0, on ? d0 : 0.0, Sx, Sxx, Sd, Sdx);
-              add_row(on ? xr[1] : 0.0, on ? d1 : 0.0, Sx, Sxx, Sd, Sdx);
-            }
-            if (i >= 4) {  // body row kd = t - 2
-              double xk = xr[(i - 2) & 7];
-              if (masked) xk = (t < e) ? xk : 0.0;
-              Sx += xk;
-              Sxx = fma(xk, xk, Sxx);
-            }
-          }
-        }
-      }
-      INSITE_TSTAMP(blockIdx.x * kWavesPerBlock + wid, 2);
-      // ---- remaining tiles of the segment (buffers alternate A, B; two tiles in flight) ----
+      // a tile of the piece's own steps: sum x and sum x^2 of the rows t < e (the lane's end of owned rows)
       auto consume = [&](int t0, const auto& v) {
         if (t0 + kGT <= Lmin) {
 #ifdef INSITE_ABLATE_GRAM_NOCOMPUTE  // profiling only: stream the samples, one add per step
@@ -931,36 +910,60 @@ __device__ __forceinline__ void gram_body(const int vblk, const int vgrid, doubl
 #endif
 #pragma unroll
           for (int i = 0; i < kGT; ++i) {
-            xr[i & 7] = sample(v, i);
-            if constexpr (SMOOTH) {
-              sr[(i - 2) & 7] = sg_int(w, xr[(i - 4) & 7], xr[(i - 3) & 7], xr[(i - 2) & 7], xr[(i - 1) & 7], xr[i & 7]);
-              add_row(xr[(i - 4) & 7], fd_int(w, sr[(i - 6) & 7], sr[(i - 5) & 7], sr[(i - 3) & 7], sr[(i - 2) & 7]),
-                      Sx, Sxx, Sd, Sdx);
-            } else {
-              const double xk = xr[(i - 2) & 7];
-              Sx += xk;
-              Sxx = fma(xk, xk, Sxx);
-            }
+            const double xk = sample(v, i);
+            Sx += xk;
+            Sxx = fma(xk, xk, Sxx);
           }
         } else {
 #pragma unroll
           for (int i = 0; i < kGT; ++i) {
-            if (t0 + i < s1) {
-              xr[i & 7] = sample(v, i);
-              const bool own = t0 + i < e;
-              if constexpr (SMOOTH) {
-                sr[(i - 2) & 7] = sg_int(w, xr[(i - 4) & 7], xr[(i - 3) & 7], xr[(i - 2) & 7], xr[(i - 1) & 7], xr[i & 7]);
-                const double dk = fd_int(w, sr[(i - 6) & 7], sr[(i - 5) & 7], sr[(i - 3) & 7], sr[(i - 2) & 7]);
-                add_row(own ? xr[(i - 4) & 7] : 0.0, own ? dk : 0.0, Sx, Sxx, Sd, Sdx);
-              } else {
-                const double xk = own ? xr[(i - 2) & 7] : 0.0;
-                Sx += xk;
-                Sxx = fma(xk, xk, Sxx);
-              }
+            if (t0 + i < s1) {  // uniform
+              const double xk = (t0 + i < e) ? sample(v, i) : 0.0;
+              Sx += xk;
+              Sxx = fma(xk, xk, Sxx);
             }
           }
         }
       };
+      // ---- first tile: steps [tb, tb + kGT); in the piece with `first` it holds the head samples ----
+      auto first_tile = [&](const auto& v) {
+        if (first) {  // head rows 0..kEdge-1 (x_dot only: the rows' x goes through consume) and the a-side terms
+          double h[kMinMain];
+#pragma unroll
+          for (int i = 0; i < kMinMain; ++i) h[i] = sample(v, i);
+          const bool on = Lm > 0;
+          if constexpr (SMOOTH) {  // from x[0..7], xs[0..5]
+            const double xs0 = sg_pos0(h[0], h[1], h[2], h[3], h[4]);
+            const double xs1 = sg_pos1(h[0], h[1], h[2], h[3], h[4]);
+            const double xs2 = sg_int(w, h[0], h[1], h[2], h[3], h[4]);
+            const double xs3 = sg_int(w, h[1], h[2], h[3], h[4], h[5]);
+            const double xs4 = sg_int(w, h[2], h[3], h[4], h[5], h[6]);
+            const double xs5 = sg_int(w, h[3], h[4], h[5], h[6], h[7]);
+            const double d0 = fd_pos0(xs0, xs1, xs2, xs3, xs4) * w.inv_dt;
+            const double d1 = fd_pos1(xs0, xs1, xs2, xs3, xs4) * w.inv_dt;
+            const double d2 = fd_int(w, xs0, xs1, xs3, xs4);
+            const double d3 = fd_int(w, xs1, xs2, xs4, xs5);
+            add_drow(on ? h[0] : 0.0, on ? d0 : 0.0, Sd, Sdx);
+            add_drow(on ? h[1] : 0.0, on ? d1 : 0.0, Sd, Sdx);
+            add_drow(on ? h[2] : 0.0, on ? d2 : 0.0, Sd, Sdx);
+            add_drow(on ? h[3] : 0.0, on ? d3 : 0.0, Sd, Sdx);
+            tele9_lo(w, h, loSd, loSdx);  // body rows a = 4 ..: x[a-4 .. a+3]
+          } else {  // from x[0..4]
+            const double d0 = fd_pos0(h[0], h[1], h[2], h[3], h[4]) * w.inv_dt;
+            const double d1 = fd_pos1(h[0], h[1], h[2], h[3], h[4]) * w.inv_dt;
+            add_drow(on ? h[0] : 0.0, on ? d0 : 0.0, Sd, Sdx);
+            add_drow(on ? h[1] : 0.0, on ? d1 : 0.0, Sd, Sdx);
+            tele_lo(w, h[0], h[1], h[2], h[3], loSd, loSdx);  // body rows a = 2 ..: x[a-2 .. a+1]
+          }
+          loSd = body ? loSd : 0.0;
+          loSdx = body ? loSdx : 0.0;
+        }
+        consume(tb, v);
+      };
+      if constexpr (TM) first_tile(vr[0]);
+      else first_tile(vA);
+      INSITE_TSTAMP(blockIdx.x * kWavesPerBlock + wid, 2);
+      // ---- remaining tiles of the piece (buffers alternate A, B; two tiles in flight) ----
       if constexpr (TM) {
         // ring slot d holds tile tb + d * kGT (mod kTmDepth); each slot is refilled with the tile
         // kTmDepth ahead right after it is consumed (compile-time slot indices: no moves)
@@ -993,7 +996,7 @@ __device__ __forceinline__ void gram_body(const int vblk, const int vgrid, doubl
           }
           if (have) {
             const int64_t np0 = np.tile * kWave;
-            const int ntb = np.s0 == 0 ? 0 : np.s0 - kWarm;
+            const int ntb = np.s0;  // (= the next piece's tb)
             const int ns1p = min(np.sE, n_steps);
             const int nvalid = (int)(N - np0 < kWave ? N - np0 : kWave);
             const unsigned noff = np0 + lane < N ? (unsigned)lane * 8u : kOOB;
@@ -1030,35 +1033,30 @@ __device__ __forceinline__ void gram_body(const int vblk, const int vgrid, doubl
       INSITE_TSTAMP(blockIdx.x * kWavesPerBlock + wid, 3);
       // ---- b-side telescoped terms and tail rows from the prefetched end samples ----
       issue_tail();
-      if (need_end) {
+      double hiSd = 0.0, hiSdx = 0.0;
+      if (tail) {  // tail rows L-kEdge..L-1 (x_dot only: the rows' x went through consume) and the b-side terms
         if constexpr (SMOOTH) {
-          const double* q = qe;  // x[e-8 .. e-1]
-          const double a0 = sg_int(w, q[0], q[1], q[2], q[3], q[4]);  // xs[e-6]
-          const double a1 = sg_int(w, q[1], q[2], q[3], q[4], q[5]);  // xs[e-5]
-          const double a2 = sg_int(w, q[2], q[3], q[4], q[5], q[6]);  // xs[e-4]
-          const double a3 = sg_int(w, q[3], q[4], q[5], q[6], q[7]);  // xs[e-3]
-          if (tail) {  // rows L-4 .. L-1: raw x[L-4 .. L-1] = q[4 .. 7]
-            const double a4 = sg_pos3(q[3], q[4], q[5], q[6], q[7]);  // xs[L-2]
-            const double a5 = sg_pos4(q[3], q[4], q[5], q[6], q[7]);  // xs[L-1]
-            add_row(q[4], fd_int(w, a0, a1, a3, a4), Sx, Sxx, Sd, Sdx);
-            add_row(q[5], fd_int(w, a1, a2, a4, a5), Sx, Sxx, Sd, Sdx);
-            add_row(q[6], fd_pos3(a1, a2, a3, a4, a5) * w.inv_dt, Sx, Sxx, Sd, Sdx);
-            add_row(q[7], fd_pos4(a1, a2, a3, a4, a5) * w.inv_dt, Sx, Sxx, Sd, Sdx);
-          }
+          const double* q = qe;  // x[L-8 .. L-1]
+          const double a0 = sg_int(w, q[0], q[1], q[2], q[3], q[4]);  // xs[L-6]
+          const double a1 = sg_int(w, q[1], q[2], q[3], q[4], q[5]);  // xs[L-5]
+          const double a2 = sg_int(w, q[2], q[3], q[4], q[5], q[6]);  // xs[L-4]
+          const double a3 = sg_int(w, q[3], q[4], q[5], q[6], q[7]);  // xs[L-3]
+          const double a4 = sg_pos3(q[3], q[4], q[5], q[6], q[7]);    // xs[L-2]
+          const double a5 = sg_pos4(q[3], q[4], q[5], q[6], q[7]);    // xs[L-1]
+          add_drow(q[4], fd_int(w, a0, a1, a3, a4), Sd, Sdx);
+          add_drow(q[5], fd_int(w, a1, a2, a4, a5), Sd, Sdx);
+          add_drow(q[6], fd_pos3(a1, a2, a3, a4, a5) * w.inv_dt, Sd, Sdx);
+          add_drow(q[7], fd_pos4(a1, a2, a3, a4, a5) * w.inv_dt, Sd, Sdx);
+          if (body) tele9_hi(w, qe, hiSd, hiSdx);  // body rows .. b = L - 5: x[b-3 .. b+4]
         } else {
-          const double* q = qe;  // x[e-5 .. e-1]
-          if (has_body) {  // body rows a..b, b = e - 3: x[b-1..b+2] = x[e-4 .. e-1]
-            double hiSd, hiSdx;
-            tele_hi(w, q[1], q[2], q[3], q[4], hiSd, hiSdx);
-            Sd += hiSd - loSd;
-            Sdx += hiSdx - loSdx;
-          }
-          if (tail) {
-            add_row(q[3], fd_pos3(q[0], q[1], q[2], q[3], q[4]) * w.inv_dt, Sx, Sxx, Sd, Sdx);
-            add_row(q[4], fd_pos4(q[0], q[1], q[2], q[3], q[4]) * w.inv_dt, Sx, Sxx, Sd, Sdx);
-          }
+          const double* q = qe;  // x[L-5 .. L-1]
+          add_drow(q[3], fd_pos3(q[0], q[1], q[2], q[3], q[4]) * w.inv_dt, Sd, Sdx);
+          add_drow(q[4], fd_pos4(q[0], q[1], q[2], q[3], q[4]) * w.inv_dt, Sd, Sdx);
+          if (body) tele_hi(w, q[1], q[2], q[3], q[4], hiSd, hiSdx);  // body rows .. b = L - 3: x[b-1 .. b+2]
         }
       }
+      Sd += hiSd - loSd;  // (one piece holding both ends takes their difference first)
+      Sdx += hiSdx - loSdx;
     }
     if constexpr (SMOOTH) {
       if (first && L > 0 && L < kMinMain) {
@@ -4399,6 +4397,7 @@ inline GramW make_gram_w(double dt) {
   w.inv_dt = 1.0 / dt;
   w.fd1 = (2.0 / 3.0) * w.inv_dt;  // 5-point first derivative [1, -8, 0, 8, -1] / 12 dt
   w.fd2 = (-1.0 / 12.0) * w.inv_dt;
+  gram_w_composite(w);
   return w;
 }
 
