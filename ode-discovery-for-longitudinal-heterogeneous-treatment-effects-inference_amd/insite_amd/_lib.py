@@ -43,6 +43,9 @@ POLICY_ABI_VERSION, POLICY_MAX_REPLICATES, POLICY_MAX_PLANS, POLICY_MAX_GROUPS, 
 # include/insite_feedback.h
 FEEDBACK_ABI_VERSION, FEEDBACK_MAX_REPLICATES, FEEDBACK_MAX_QUANTILES, FEEDBACK_MAX_RULES = 1, 512, 16, 16
 FEEDBACK_MINIMIZE, FEEDBACK_MAXIMIZE = 1, -1
+# include/insite_rulevalue.h
+RULEVALUE_ABI_VERSION = 1
+RULEVALUE_MAX_REPLICATES, RULEVALUE_MAX_RULES, RULEVALUE_MAX_GROUPS, RULEVALUE_MAX_QUANTILES = 4096, 16, 64, 16
 METHOD_EULER, METHOD_RK4 = 0, 1
 LAYOUT_PATIENT_MAJOR, LAYOUT_TIME_MAJOR, LAYOUT_TIME_MAJOR_BITS, LAYOUT_PATIENT_MAJOR_BITS = 0, 1, 2, 3
 MAX_TERMS, MAX_STATICS, MAX_ARMS, MAX_STATE_DEGREE = 9, 3, 4, 1
@@ -162,6 +165,17 @@ POLICY_EXPORTS = (
 FEEDBACK_SYMBOLS = (
     "insite_feedback_abi_version",
     "insite_feedback_rules_f64",
+)
+
+# the extension header include/insite_rulevalue.h (same shared library, its own ABI version).  Not named *_EXPORTS
+# either: tests/test_workspace_matrix.py pins the set of names with that ending.  The sums and the fused call take a
+# workspace, but before their outputs (the header says why)
+RULEVALUE_SYMBOLS = (
+    "insite_rulevalue_abi_version",
+    "insite_rulevalue_workspace_bytes",
+    "insite_rulevalue_sums_f64",
+    "insite_rulevalue_finalize_f64",
+    "insite_rulevalue_f64",
 )
 
 
@@ -337,6 +351,19 @@ _SIGNATURES = {
     "insite_feedback_rules_f64": (_c_i32, [_vp, _vp, _vp, _c_i64, _vp, _c_i32, _vp, _c_i64, _vp, _vp, _c_i32, _vp, _vp,
                                            _c_i32, _c_i64, _c_i32, _c_i32, _c_i32, _c_f64, _c_i32, _c_i32, _c_f64,
                                            _c_i32, _vp, _c_i32, _vp, _vp, _vp, _c_i64, _vp, _c_i64, _vp]),
+    # insite_rulevalue.h
+    "insite_rulevalue_abi_version": (_c_i32, []),
+    "insite_rulevalue_workspace_bytes": (_c_size, [_c_i64, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32]),
+    "insite_rulevalue_sums_f64": (_c_i32, [_vp, _vp, _vp, _c_i64, _vp, _c_i32, _vp, _c_i64, _vp, _vp, _c_i32, _vp, _vp,
+                                           _c_i32, _c_i64, _c_i32, _c_i32, _c_i32, _c_f64, _c_i32, _c_i32, _c_f64,
+                                           _c_i32, _vp, _c_i32, _c_i32, ctypes.c_uint32, _c_i64, _vp, _vp, _vp, _c_size,
+                                           _vp, _vp, _vp]),
+    "insite_rulevalue_finalize_f64": (_c_i32, [_vp, _vp, _c_i32, _c_i32, _c_i32, _c_i32, _vp, _c_i32, _vp, _c_i64,
+                                               _vp, _vp, _vp]),
+    "insite_rulevalue_f64": (_c_i32, [_vp, _vp, _vp, _c_i64, _vp, _c_i32, _vp, _c_i64, _vp, _vp, _c_i32, _vp, _vp,
+                                           _c_i32, _c_i64, _c_i32, _c_i32, _c_i32, _c_f64, _c_i32, _c_i32, _c_f64,
+                                           _c_i32, _vp, _c_i32, _c_i32, ctypes.c_uint32, _c_i64, _vp, _vp, _vp, _c_size,
+                                           _vp, _vp, _vp, _c_i32, _vp, _c_i64, _vp, _vp, _vp]),
 }
 
 # (getter, the version these bindings were written for, the label of the mismatch message)
@@ -350,6 +377,7 @@ _ABI_VERSIONS = (
     ("insite_regimen_abi_version", REGIMEN_ABI_VERSION, "regimen "),
     ("insite_policy_abi_version", POLICY_ABI_VERSION, "policy "),
     ("insite_feedback_abi_version", FEEDBACK_ABI_VERSION, "feedback "),
+    ("insite_rulevalue_abi_version", RULEVALUE_ABI_VERSION, "rulevalue "),
 )
 
 

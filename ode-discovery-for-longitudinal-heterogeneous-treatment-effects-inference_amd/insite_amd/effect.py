@@ -244,3 +244,76 @@ def from_policy(out: torch.Tensor, fixwin: torch.Tensor, best_fixed: torch.Tenso
     return PolicyValueResult(point=res[:, 0], mean=res[:, 1], std=res[:, 2], quantiles=res[:, 3:], fixwin=fixwin,
                              best_fixed=best_fixed, rule=rule, weight_sum=wsum, q=tuple(float(v) for v in q),
                              series=policy_series(K), n_plans=K)
+
+
+def rule_value_series(n_rules: int) -> tuple:
+    """The names of the 3 K + 9 series of ``ops.rule_value`` in the order of include/insite_rulevalue.h."""
+    K = int(n_rules)
+    return (tuple(f"value_{j}" for j in range(K))
+            + ("personalised", "assigned", "best_fixed", "gain_personalised", "gain_assigned", "optimism")
+            + tuple(f"share_{j}" for j in range(K)) + tuple(f"exposure_{j}" for j in range(K))
+            + ("exposure_personalised", "exposure_assigned", "exposure_best_fixed"))
+
+
+@dataclasses.dataclass
+class RuleValueResult:
+    """The cohort value of K closed-loop rules of ``ops.rule_value`` (include/insite_rulevalue.h).
+    ``series``: ``rule_value_series(K)`` -- value_j (everyone follows rule j), personalised (every row its own best
+    rule, re-derived inside each replicate), assigned (the fixed per-row ``assign`` under each replicate's model),
+    best_fixed (the best single rule of the replicate), gain_personalised = best_fixed - personalised, gain_assigned =
+    best_fixed - assigned and optimism = assigned - personalised (signed by the sense: the first and the last are
+    >= 0), share_j (the weight share of the rows whose best rule is j), exposure_j (the treated steps per row when
+    everyone follows rule j), exposure_personalised, exposure_assigned and exposure_best_fixed.  ``point``, ``mean``,
+    ``std`` [S, G]: per group the point model's value and the mean / standard deviation (n - 1 divisor) over the
+    replicates 1..R-1; ``quantiles`` [S, Q, G] in the order of ``q``.  ``fixwin`` [G, K]: the share of the replicates
+    in which rule j is the best fixed rule; ``best_fixed`` int32 [G]: the point model's (-1: it has a NaN value);
+    ``assign`` int32 [N]; ``weight_sum`` [R, G].  ``result["optimism"]`` gives one series as a dict,
+    ``result.share`` the K share series as [K, G] statistics, ``result.exposure`` the K + 3 exposure series as
+    [K + 3, G] statistics."""
+    point: torch.Tensor
+    mean: torch.Tensor
+    std: torch.Tensor
+    quantiles: torch.Tensor
+    fixwin: torch.Tensor
+    best_fixed: torch.Tensor
+    assign: torch.Tensor
+    weight_sum: torch.Tensor
+    q: tuple
+    series: tuple
+    n_rules: int
+
+    def __getitem__(self, name: str) -> dict:
+        i = self.series.index(name)
+        return {"point": self.point[i], "mean": self.mean[i], "std": self.std[i], "quantiles": self.quantiles[i]}
+
+    def _block(self, lo, hi) -> dict:
+        return {"point": self.point[lo:hi], "mean": self.mean[lo:hi], "std": self.std[lo:hi],
+                "quantiles": self.quantiles[lo:hi].transpose(0, 1)}
+
+    @property
+    def share(self) -> dict:
+        return self._block(self.n_rules + 6, 2 * self.n_rules + 6)
+
+    @property
+    def exposure(self) -> dict:
+        return self._block(2 * self.n_rules + 6, 3 * self.n_rules + 9)
+
+
+def from_rule_value(out: torch.Tensor, fixwin: torch.Tensor, best_fixed: torch.Tensor, assign: torch.Tensor,
+                    wsum: torch.Tensor, q, shift: float = 0.0, scale: float = 1.0) -> RuleValueResult:
+    """``ops.rule_value``'s outputs as a ``RuleValueResult`` in the scale (x - shift) / scale, by ``from_policy``'s
+    rule: the locations (point, mean, quantiles) of the value, personalised, assigned and best_fixed series are
+    shifted and divided, their standard deviations and every statistic of the three differences (the shift cancels)
+    are divided only, the shares and the exposures (counts of steps) are left as they are.  ``shift``: the mean times
+    the weight total of a row's steps."""
+    if out.dim() != 3 or out.size(1) < 12 or out.size(1) % 3 or out.size(2) != 3 + len(q):
+        raise ValueError("out must be [G, 3 K + 9, 3 + Q]")
+    K = out.size(1) // 3 - 3
+    o = out.permute(1, 2, 0)                        # [S, 3 + Q, G]
+    res = o.clone()
+    loc = [0, 1] + list(range(3, o.size(1)))        # point, mean and quantiles
+    res[:K + 6] = o[:K + 6] / scale
+    res[:K + 3, loc] = (o[:K + 3, loc] - shift) / scale
+    return RuleValueResult(point=res[:, 0], mean=res[:, 1], std=res[:, 2], quantiles=res[:, 3:], fixwin=fixwin,
+                           best_fixed=best_fixed, assign=assign, weight_sum=wsum, q=tuple(float(v) for v in q),
+                           series=rule_value_series(K), n_rules=K)

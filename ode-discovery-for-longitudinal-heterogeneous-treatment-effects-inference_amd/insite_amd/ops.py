@@ -1097,15 +1097,15 @@ def plan_regimen_choice(y0, u, plans, coef, lib, dt, quantiles, weights, cost=No
     return Plan(name, args, dev, outs, keep)
 
 
-def _prep_feedback_rules(y0, u, theta, rules, coef, lib, dt, quantiles, weights, cost, arm_cost, maximize, method,
-                         substeps, drop_below, T, out, sched):
-    """Validate the inputs of the closed-loop rules and pack the C arguments (insite_feedback.h)."""
-    _lib.load()
+def _check_rules_inputs(y0, u, theta, rules, coef, lib, weights, cost, arm_cost, T, max_rules, max_replicates):
+    """What the closed-loop rules and their cohort value check first, in this order: the host rule table, y0, the step
+    weights, the thresholds, cost, the statics and the ensemble, the rules' fields, arm_cost.  Returns
+    (rl int32 [K, 4], ac f64 [A] or None, N, K, T, R, A, ld_theta, ld_w)."""
     rl = np.ascontiguousarray(np.asarray(rules, dtype=np.int64).reshape(-1, 4) if np.size(rules) else
                               np.zeros((0, 4), dtype=np.int64))
     K = rl.shape[0]
-    if not 1 <= K <= _lib.FEEDBACK_MAX_RULES:
-        raise ValueError(f"between 1 and {_lib.FEEDBACK_MAX_RULES} rules (arm_on, arm_off, period, start_on) expected, "
+    if not 1 <= K <= max_rules:
+        raise ValueError(f"between 1 and {max_rules} rules (arm_on, arm_off, period, start_on) expected, "
                          f"got {K}")
     _dev("y0", y0, torch.float64, 1)
     N = y0.numel()
@@ -1128,7 +1128,7 @@ def _prep_feedback_rules(y0, u, theta, rules, coef, lib, dt, quantiles, weights,
         _dev("cost", cost, torch.float64, 1)
         if cost.numel() != K or not cost.is_contiguous():
             raise ValueError("cost must be a contiguous f64 [K] tensor")
-    R, A = _check_statics_coef(u, coef, lib, N, _lib.FEEDBACK_MAX_REPLICATES)
+    R, A = _check_statics_coef(u, coef, lib, N, max_replicates)
     if (rl[:, :2] < 0).any() or (rl[:, :2] >= A).any() or (rl[:, 2] < 1).any() or (rl[:, 2] > 2**31 - 1).any() \
             or ((rl[:, 3] != 0) & (rl[:, 3] != 1)).any():
         raise ValueError(f"rules: arm_on and arm_off must lie in [0, {A}), period must be >= 1, start_on 0 or 1")
@@ -1138,6 +1138,16 @@ def _prep_feedback_rules(y0, u, theta, rules, coef, lib, dt, quantiles, weights,
         ac = np.ascontiguousarray(np.asarray(arm_cost, dtype=np.float64))
         if ac.shape != (A,):
             raise ValueError(f"arm_cost must hold one number per arm ({A})")
+    return rl, ac, N, K, T, R, A, ld_theta, ld_w
+
+
+def _prep_feedback_rules(y0, u, theta, rules, coef, lib, dt, quantiles, weights, cost, arm_cost, maximize, method,
+                         substeps, drop_below, T, out, sched):
+    """Validate the inputs of the closed-loop rules and pack the C arguments (insite_feedback.h)."""
+    _lib.load()
+    rl, ac, N, K, T, R, A, ld_theta, ld_w = _check_rules_inputs(y0, u, theta, rules, coef, lib, weights, cost, arm_cost,
+                                                                T, _lib.FEEDBACK_MAX_RULES,
+                                                                _lib.FEEDBACK_MAX_REPLICATES)
     F = lib.n_terms
     q = _quantiles(quantiles, _lib.FEEDBACK_MAX_QUANTILES)
     m, sub = _method(method, substeps)
@@ -1491,6 +1501,170 @@ def plan_policy_value(y0, u, plans, coef, lib, dt, quantiles, weights, cost=None
     name, args, dev, outs, keep = _prep_policy(y0, u, plans, coef, lib, dt, quantiles, weights, cost, maximize, rule,
                                                group, n_groups, weighting, seed, patient_offset, method, substeps,
                                                drop_below, T, out, ws, None)
+    return Plan(name, args, dev, outs, keep)
+
+
+def _rule_value_stats_out(out, G, K, Q, dev):
+    """out [G, 3 K + 9, >= 3 + Q] (the statistics may be padded, everything else dense) and its leading dimension."""
+    S, NS = 3 * K + 9, 3 + Q
+    if out is None:
+        return torch.empty((G, S, NS), dtype=torch.float64, device=dev), NS
+    _dev("out", out, torch.float64, 3)
+    ld = out.stride(1)
+    if tuple(out.shape) != (G, S, NS) or ld < NS or (G > 1 and out.stride(0) != S * ld):
+        raise ValueError(f"out must be {(G, S, NS)} with a dense leading dimension (the statistics may be padded)")
+    return out, ld
+
+
+def _prep_rule_value(y0, u, theta, rules, coef, lib, dt, quantiles, weights, cost, arm_cost, maximize, assign, group,
+                     n_groups, weighting, seed, patient_offset, method, substeps, drop_below, T, out, workspace,
+                     sums_out):
+    """Validate the inputs of the rule value and pack the C arguments (insite_rulevalue.h); ``quantiles`` None: the
+    sums call alone."""
+    L = _lib.load()
+    rl, ac, N, K, T, R, A, ld_theta, ld_w = _check_rules_inputs(y0, u, theta, rules, coef, lib, weights, cost, arm_cost,
+                                                                T, _lib.RULEVALUE_MAX_RULES,
+                                                                _lib.RULEVALUE_MAX_REPLICATES)
+    F = lib.n_terms
+    G = int(n_groups)
+    if not 1 <= G <= _lib.RULEVALUE_MAX_GROUPS:
+        raise ValueError(f"n_groups must be in [1, {_lib.RULEVALUE_MAX_GROUPS}]")
+    if group is not None:
+        _dev("group", group, torch.int32, 1)
+        if group.numel() != N:
+            raise ValueError("group must have one entry per row")
+    if weighting not in COHORT_WEIGHTINGS:
+        raise ValueError(f"weighting must be one of {sorted(COHORT_WEIGHTINGS)}")
+    if not 0 <= int(seed) < 2 ** 32:
+        raise ValueError("seed must be a uint32")
+    if int(patient_offset) < 0:
+        raise ValueError("patient_offset must be >= 0")
+    m, sub = _method(method, substeps)
+    dev = y0.device
+    assign_out = None
+    if assign is not None:
+        _dev("assign", assign, torch.int32, 1)
+        if assign.numel() != N or not assign.is_contiguous():
+            raise ValueError("assign must be a contiguous int32 tensor with one entry per row")
+    else:
+        assign_out = torch.full((N,), -1, dtype=torch.int32, device=dev)
+    C = 3 * K + 4
+    if sums_out is None:
+        sums_out = (torch.zeros((R, G, C), dtype=torch.float64, device=dev),
+                    torch.zeros((R, G), dtype=torch.float64, device=dev))
+    sums, wsum = sums_out
+    _dev("sums", sums, torch.float64, 3)
+    _dev("wsum", wsum, torch.float64, 2)
+    if tuple(sums.shape) != (R, G, C) or not sums.is_contiguous():
+        raise ValueError(f"sums must be a contiguous {(R, G, C)} tensor")
+    if tuple(wsum.shape) != (R, G) or not wsum.is_contiguous():
+        raise ValueError(f"wsum must be a contiguous {(R, G)} tensor")
+    ws_bytes = L.insite_rulevalue_workspace_bytes(N, T, A, F, R, G, K)
+    ws = _ws(workspace, dev, "scratch").get(ws_bytes, dev)
+    tab = lib.ctypes_table()
+    # (the workspace stands before the outputs: the header says why)
+    head = (_p(y0), _p(u) if lib.n_statics else ctypes.c_void_p(0), _p(theta), ld_theta,
+            rl.ctypes.data_as(ctypes.c_void_p), K, _p(weights), ld_w, _p(cost),
+            ac.ctypes.data_as(ctypes.c_void_p) if ac is not None else ctypes.c_void_p(0),
+            _lib.FEEDBACK_MAXIMIZE if maximize else _lib.FEEDBACK_MINIMIZE, _p(coef),
+            tab.ctypes.data_as(ctypes.c_void_p), F, N, T, lib.n_statics, A, float(dt), m, sub, float(drop_below), R,
+            _p(group), G, COHORT_WEIGHTINGS[weighting], int(seed), int(patient_offset), _p(assign), _p(assign_out),
+            _p(ws), ws_bytes, _p(sums), _p(wsum))
+    keep = (y0, u, theta, rl, weights, cost, ac, coef, group, assign, assign_out, tab, ws, sums, wsum)
+    the_assign = assign if assign is not None else assign_out
+    if quantiles is None:
+        return "insite_rulevalue_sums_f64", head, dev, (sums, wsum, the_assign), keep
+    q = _quantiles(quantiles, _lib.RULEVALUE_MAX_QUANTILES)
+    out, ld_out = _rule_value_stats_out(out, G, K, q.size, dev)
+    fixwin = torch.zeros((G, K), dtype=torch.float64, device=dev)
+    best_fixed = torch.full((G,), -1, dtype=torch.int32, device=dev)
+    args = head + (q.ctypes.data_as(ctypes.c_void_p), q.size, _p(out), ld_out, _p(fixwin), _p(best_fixed))
+    return ("insite_rulevalue_f64", args, dev, (out, fixwin, best_fixed, the_assign, sums, wsum),
+            keep + (q, out, fixwin, best_fixed))
+
+
+def rule_value_sums(y0: torch.Tensor, u: torch.Tensor, theta: torch.Tensor, rules, coef: torch.Tensor,
+                    lib: PolyLibrary, dt: float, weights: torch.Tensor, cost: torch.Tensor | None = None,
+                    arm_cost=None, maximize: bool = False, assign: torch.Tensor | None = None,
+                    group: torch.Tensor | None = None, n_groups: int = 1, weighting: str = "poisson", seed: int = 0,
+                    patient_offset: int = 0, method: str = "euler5", substeps: int | None = None,
+                    drop_below: float = 1e-3, T: int | None = None, out: tuple | None = None,
+                    workspace: Workspace | None = None):
+    """The weighted closed-loop sums of a cohort or of one shard of it (insite_rulevalue_sums_f64):
+    (sums [R, G, 3 K + 4], wsum [R, G], assign int32 [N]).  Columns of sums: K fixed-rule values, the personalised
+    rule re-derived in the replicate, the given ``assign`` (None: the point model's choice, computed and returned), K
+    allocation counts, K exposures (treated steps), the exposures of the personalised and of the assigned rule.  sums
+    and wsum are additive over shards (``patient_offset``: the index of row 0 in the whole cohort);
+    ``rule_value_finalize`` turns their total into the statistics.  With no rows nothing is written: fresh outputs are
+    zero."""
+    return _run(_prep_rule_value(y0, u, theta, rules, coef, lib, dt, None, weights, cost, arm_cost, maximize, assign,
+                                 group, n_groups, weighting, seed, patient_offset, method, substeps, drop_below, T,
+                                 None, workspace, out))
+
+
+def rule_value_finalize(sums: torch.Tensor, wsum: torch.Tensor, quantiles, maximize: bool = False,
+                        out: torch.Tensor | None = None):
+    """The statistics of the 3 K + 9 series from ``rule_value_sums``' (all-reduced) arrays
+    (insite_rulevalue_finalize_f64): (out [G, 3 K + 9, 3 + Q], fixwin [G, K], best_fixed int32 [G])."""
+    L = _lib.load()
+    _dev("sums", sums, torch.float64, 3)
+    _dev("wsum", wsum, torch.float64, 2)
+    R, G, C = sums.shape
+    if (not sums.is_contiguous() or not wsum.is_contiguous() or tuple(wsum.shape) != (R, G) or C < 7 or (C - 4) % 3
+            or (C - 4) // 3 > _lib.RULEVALUE_MAX_RULES):
+        raise ValueError("sums / wsum must be contiguous [R, G, 3 K + 4] / [R, G] tensors, "
+                         f"K <= {_lib.RULEVALUE_MAX_RULES}")
+    K = (C - 4) // 3
+    if not 2 <= R <= _lib.RULEVALUE_MAX_REPLICATES:
+        raise ValueError(f"n_replicates must be in [2, {_lib.RULEVALUE_MAX_REPLICATES}] "
+                         "(replicate 0 is the point model)")
+    if not 1 <= G <= _lib.RULEVALUE_MAX_GROUPS:
+        raise ValueError(f"n_groups must be in [1, {_lib.RULEVALUE_MAX_GROUPS}]")
+    q = _quantiles(quantiles, _lib.RULEVALUE_MAX_QUANTILES)
+    dev = sums.device
+    out, ld_out = _rule_value_stats_out(out, G, K, q.size, dev)
+    fixwin = torch.zeros((G, K), dtype=torch.float64, device=dev)
+    best_fixed = torch.full((G,), -1, dtype=torch.int32, device=dev)
+    st = L.insite_rulevalue_finalize_f64(_p(sums), _p(wsum), R, G, K,
+                                         _lib.FEEDBACK_MAXIMIZE if maximize else _lib.FEEDBACK_MINIMIZE,
+                                         q.ctypes.data_as(ctypes.c_void_p), q.size, _p(out), ld_out, _p(fixwin),
+                                         _p(best_fixed), _stream(dev))
+    _lib.check("insite_rulevalue_finalize_f64", st)
+    return out, fixwin, best_fixed
+
+
+def rule_value(y0: torch.Tensor, u: torch.Tensor, theta: torch.Tensor, rules, coef: torch.Tensor, lib: PolyLibrary,
+               dt: float, quantiles, weights: torch.Tensor, cost: torch.Tensor | None = None, arm_cost=None,
+               maximize: bool = False, assign: torch.Tensor | None = None, group: torch.Tensor | None = None,
+               n_groups: int = 1, weighting: str = "poisson", seed: int = 0, patient_offset: int = 0,
+               method: str = "euler5", substeps: int | None = None, drop_below: float = 1e-3, T: int | None = None,
+               out: torch.Tensor | None = None, workspace: Workspace | None = None):
+    """What a cohort, and every subgroup, gains under K closed-loop rules, with bootstrap bands
+    (insite_rulevalue_f64).
+
+    ``theta``, ``rules``, ``weights``, ``cost``, ``arm_cost``, ``maximize`` as in ``feedback_rules``; ``group``,
+    ``n_groups``, ``weighting``, ``seed``, ``patient_offset`` as in ``cohort_effect``; ``assign`` int32 [N] (a rule per
+    row) or None (the point model's choice).  Returns (out [G, 3 K + 9, 3 + Q], fixwin [G, K], best_fixed int32 [G],
+    assign int32 [N], sums [R, G, 3 K + 4], wsum [R, G]).  Series of out: value_0..value_{K-1} (everyone follows rule
+    j), personalised (every row its best rule, re-derived inside each replicate), assigned (the fixed assignment under
+    each replicate's model), best_fixed, gain_personalised, gain_assigned, optimism, share_0..share_{K-1},
+    exposure_0..exposure_{K-1} (treated steps per row), exposure_personalised, exposure_assigned,
+    exposure_best_fixed; each as the point model's value, then mean, standard deviation (ddof 1) and the ``quantiles``
+    over the replicates 1..R-1.  The per-replicate objectives never exist in memory.  With no rows nothing is
+    written."""
+    return _run(_prep_rule_value(y0, u, theta, rules, coef, lib, dt, quantiles, weights, cost, arm_cost, maximize,
+                                 assign, group, n_groups, weighting, seed, patient_offset, method, substeps, drop_below,
+                                 T, out, workspace, None))
+
+
+def plan_rule_value(y0, u, theta, rules, coef, lib, dt, quantiles, weights, cost=None, arm_cost=None, maximize=False,
+                    assign=None, group=None, n_groups=1, weighting="poisson", seed=0, patient_offset=0,
+                    method="euler5", substeps=None, drop_below=1e-3, T=None, out=None, workspace=None) -> Plan:
+    """``rule_value`` as a prepared launch; ``plan.out`` = (out, fixwin, best_fixed, assign, sums, wsum)."""
+    ws = workspace.claim("scratch") if workspace is not None else Workspace("scratch")
+    name, args, dev, outs, keep = _prep_rule_value(y0, u, theta, rules, coef, lib, dt, quantiles, weights, cost,
+                                                   arm_cost, maximize, assign, group, n_groups, weighting, seed,
+                                                   patient_offset, method, substeps, drop_below, T, out, ws, None)
     return Plan(name, args, dev, outs, keep)
 
 

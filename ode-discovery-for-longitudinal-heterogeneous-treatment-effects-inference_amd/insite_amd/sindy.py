@@ -624,6 +624,32 @@ class SINDY:
                                    scale=std)
 
     # ------------------------------------------------------------------ closed-loop rules
+    def _rule_table(self, what, dataset, rules, costs, arm_costs, max_rules):
+        """A list of ``effect.ThresholdRule`` -> (the host table [(arm_on, arm_off, every, start_on)], the thresholds
+        [N, 2 K] in the units of ``get_predictions``), with the checks of ``costs`` and ``arm_costs``."""
+        if (not isinstance(rules, (list, tuple)) or not 1 <= len(rules) <= max_rules
+                or not all(isinstance(r, effect.ThresholdRule) for r in rules)):
+            raise ValueError(f"{what}: rules must be a list of 1 to {max_rules} "
+                             "effect.ThresholdRule")
+        K = len(rules)
+        if costs is not None and np.asarray(costs, dtype=np.float64).shape != (K,):
+            raise ValueError(f"{what}: costs must hold one number per rule ({K})")
+        A = self.dim_treatments
+        if arm_costs is not None and np.asarray(arm_costs, dtype=np.float64).shape != (A,):
+            raise ValueError(f"{what}: arm_costs must hold one number per arm ({A})")
+        N = dataset.data["current_treatments"].shape[0]
+        table, th = [], np.empty((N, 2 * K))
+        for j, r in enumerate(rules):
+            if not (0 <= int(r.arm_on) < A and 0 <= int(r.arm_off) < A) or int(r.every) < 1:
+                raise ValueError(f"{what}: rules[{j}]: arms must lie in [0, {A}) and every must be >= 1")
+            table.append((int(r.arm_on), int(r.arm_off), int(r.every), 1 if r.start_on else 0))
+            for c, v in ((2 * j, r.on), (2 * j + 1, r.on if r.off is None else r.off)):
+                v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, dtype=np.float64)
+                if v.shape not in ((), (N,)):
+                    raise ValueError(f"{what}: rules[{j}]: a threshold is a number or an array [{N}]")
+                th[:, c] = v
+        return table, th
+
     def evaluate_rules(self, dataset, rules, objective="mean", costs=None, arm_costs=None, maximize=False,
                        quantiles=(0.025, 0.5, 0.975), schedule=False):
         """How each of the closed-loop ``rules`` does for every row of ``dataset``, and how sure the bootstrap ensemble
@@ -638,27 +664,7 @@ class SINDY:
         with ``schedule`` also the arms the point model applies, int8 [N, K, T], which ``treatment_effect`` and
         ``choose_plan`` take as plans.  One launch of ``ops.feedback_rules``."""
         coef = self._effect_coef("evaluate_rules", _lib.FEEDBACK_MAX_REPLICATES)
-        if (not isinstance(rules, (list, tuple)) or not 1 <= len(rules) <= _lib.FEEDBACK_MAX_RULES
-                or not all(isinstance(r, effect.ThresholdRule) for r in rules)):
-            raise ValueError(f"evaluate_rules: rules must be a list of 1 to {_lib.FEEDBACK_MAX_RULES} "
-                             "effect.ThresholdRule")
-        K = len(rules)
-        if costs is not None and np.asarray(costs, dtype=np.float64).shape != (K,):
-            raise ValueError(f"evaluate_rules: costs must hold one number per rule ({K})")
-        A = self.dim_treatments
-        if arm_costs is not None and np.asarray(arm_costs, dtype=np.float64).shape != (A,):
-            raise ValueError(f"evaluate_rules: arm_costs must hold one number per arm ({A})")
-        N = dataset.data["current_treatments"].shape[0]
-        table, th = [], np.empty((N, 2 * K))
-        for j, r in enumerate(rules):
-            if not (0 <= int(r.arm_on) < A and 0 <= int(r.arm_off) < A) or int(r.every) < 1:
-                raise ValueError(f"evaluate_rules: rules[{j}]: arms must lie in [0, {A}) and every must be >= 1")
-            table.append((int(r.arm_on), int(r.arm_off), int(r.every), 1 if r.start_on else 0))
-            for c, v in ((2 * j, r.on), (2 * j + 1, r.on if r.off is None else r.off)):
-                v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, dtype=np.float64)
-                if v.shape not in ((), (N,)):
-                    raise ValueError(f"evaluate_rules: rules[{j}]: a threshold is a number or an array [{N}]")
-                th[:, c] = v
+        table, th = self._rule_table("evaluate_rules", dataset, rules, costs, arm_costs, _lib.FEEDBACK_MAX_RULES)
         prev, stat, std, mean = self._unscaled_inputs(dataset)
         theta = torch.as_tensor(th * std + mean, device=self.device)
         w = torch.as_tensor(np.ascontiguousarray(self._objective_weights(dataset, objective)), device=self.device)
@@ -744,6 +750,30 @@ class SINDY:
         return effect.from_cohort(out, wsum, quantiles, shift=mean, scale=std)
 
     # ------------------------------------------------------------------ policy value
+    def _cohort_objective(self, what, dataset, objective, groups):
+        """The step weights of a cohort value and what their shift needs: (w f64 [T] or [N, T] on the host, the one
+        sum_k w of the cohort, the group ids with the rows that have no active entry excluded)."""
+        N = dataset.data["current_treatments"].shape[0]
+        w = self._objective_weights(dataset, objective)
+        tot = np.broadcast_to(w.sum(axis=-1), (N,)) if w.ndim == 2 else np.full(N, w.sum())
+        g = None if groups is None else (groups.detach().cpu().numpy() if isinstance(groups, torch.Tensor)
+                                         else np.asarray(groups))
+        if isinstance(objective, str):
+            # a row with no active entry has no objective: excluded (its weights are all zero)
+            empty = ~(np.asarray(dataset.data["active_entries"][..., 0]) > 0).any(axis=1)
+            if empty.any():
+                if g is None:
+                    g = np.zeros(N, dtype=np.int64)
+                elif g.shape != (N,) or not np.issubdtype(g.dtype, np.integer):
+                    raise ValueError(f"groups: expected None or an int array [{N}] of group ids")
+                g = np.where(empty, -1, g)
+            tot = tot[~empty]
+        wtot = float(tot[0]) if tot.size else 0.0
+        if tot.size and float(np.max(tot) - np.min(tot)) > 1e-12 * max(float(np.max(np.abs(tot))), 1e-300):
+            raise ValueError(f"{what}: the rows of an [N, T] objective must all have the same sum (the cohort "
+                             "value is standardised with one sum_k w): normalise every row's weights to one total")
+        return w, wtot, g
+
     def policy_value(self, dataset, plans, rule=None, objective="mean", costs=None, maximize=False, groups=None,
                      quantiles=(0.025, 0.5, 0.975), resample="paired", seed=None):
         """What the cohort (and every subgroup) gains if every row gets its own best plan of ``plans`` instead of
@@ -772,24 +802,7 @@ class SINDY:
                                                                                           or rl.max() >= K)):
                 raise ValueError(f"policy_value: rule must be None or an int array [{N}] of plan indices in [0, {K})")
             rule_t = torch.as_tensor(np.ascontiguousarray(rl.astype(np.int32)), device=self.device)
-        w = self._objective_weights(dataset, objective)
-        tot = np.broadcast_to(w.sum(axis=-1), (N,)) if w.ndim == 2 else np.full(N, w.sum())
-        g = None if groups is None else (groups.detach().cpu().numpy() if isinstance(groups, torch.Tensor)
-                                         else np.asarray(groups))
-        if isinstance(objective, str):
-            # a row with no active entry has no objective: excluded (its weights are all zero)
-            empty = ~(np.asarray(dataset.data["active_entries"][..., 0]) > 0).any(axis=1)
-            if empty.any():
-                if g is None:
-                    g = np.zeros(N, dtype=np.int64)
-                elif g.shape != (N,) or not np.issubdtype(g.dtype, np.integer):
-                    raise ValueError(f"groups: expected None or an int array [{N}] of group ids")
-                g = np.where(empty, -1, g)
-            tot = tot[~empty]
-        wtot = float(tot[0]) if tot.size else 0.0
-        if tot.size and float(np.max(tot) - np.min(tot)) > 1e-12 * max(float(np.max(np.abs(tot))), 1e-300):
-            raise ValueError("policy_value: the rows of an [N, T] objective must all have the same sum (the cohort "
-                             "value is standardised with one sum_k w): normalise every row's weights to one total")
+        w, wtot, g = self._cohort_objective("policy_value", dataset, objective, groups)
         group, n_groups = self._groups(g, N)
         prev, stat, std, mean = self._unscaled_inputs(dataset)
         arms = torch.stack([self._plan_arms(dataset, pl, f"plans[{j}]") for j, pl in enumerate(plans)]).contiguous()
@@ -802,6 +815,49 @@ class SINDY:
             maximize=maximize, rule=rule_t, group=group, n_groups=n_groups, weighting=weighting, seed=use_seed,
             method=self.integrator, drop_below=0.0, T=arms.size(2))
         return effect.from_policy(out, fixwin, best_fixed, rule_o, wsum, quantiles, shift=mean * wtot, scale=std)
+
+    # ------------------------------------------------------------------ rule value
+    def rule_value(self, dataset, rules, assignment=None, objective="mean", costs=None, arm_costs=None,
+                   maximize=False, groups=None, quantiles=(0.025, 0.5, 0.975), resample="paired", seed=None):
+        """What the cohort (and every subgroup) gains under each of the closed-loop ``rules``, what it gains if every
+        row gets its own best rule instead of everyone following the best single rule, and how many treated steps
+        per row each policy costs, with bands from ``bootstrap_``.  ``rules``, ``objective``, ``costs``,
+        ``arm_costs`` and ``maximize`` are ``evaluate_rules``'; ``groups``, ``resample`` and ``seed`` are
+        ``average_effect``'s.  ``assignment``: None (the point model's choice, ``evaluate_rules(...).choice``) or an
+        int array [N] of rule indices in [0, K): the fixed per-row assignment that every replicate's model evaluates.
+        Returns an ``effect.RuleValueResult``: the series value_j, personalised, assigned and best_fixed in
+        ``evaluate_rules``' units ((J - mean sum_k w) / std), gain_personalised, gain_assigned and optimism divided by
+        the output's standard deviation only, share_j and the exposures (treated steps per row) not rescaled.  An
+        [N, T] ``objective`` whose rows do not all have the same sum is refused; under "mean" / "terminal" a row with
+        no active entry is excluded, as in ``policy_value``.  One launch of ``ops.rule_value``."""
+        coef = self._effect_coef("rule_value", _lib.RULEVALUE_MAX_REPLICATES)
+        weighting, use_seed = self._resample("rule_value", resample, seed)
+        table, th = self._rule_table("rule_value", dataset, rules, costs, arm_costs, _lib.RULEVALUE_MAX_RULES)
+        K = len(table)
+        N = dataset.data["current_treatments"].shape[0]
+        assign_t = None
+        if assignment is not None:
+            al = assignment.detach().cpu().numpy() if isinstance(assignment, torch.Tensor) else np.asarray(assignment)
+            if al.shape != (N,) or not np.issubdtype(al.dtype, np.integer) or (al.size and (al.min() < 0
+                                                                                          or al.max() >= K)):
+                raise ValueError(f"rule_value: assignment must be None or an int array [{N}] of rule indices in "
+                                 f"[0, {K})")
+            assign_t = torch.as_tensor(np.ascontiguousarray(al.astype(np.int32)), device=self.device)
+        w, wtot, g = self._cohort_objective("rule_value", dataset, objective, groups)
+        group, n_groups = self._groups(g, N)
+        prev, stat, std, mean = self._unscaled_inputs(dataset)
+        theta = torch.as_tensor(th * std + mean, device=self.device)
+        wt = torch.as_tensor(np.ascontiguousarray(w), device=self.device)
+        cost = None
+        if costs is not None:
+            cost = torch.as_tensor(np.asarray(costs, dtype=np.float64) * std, device=self.device)
+        ac = None if arm_costs is None else np.asarray(arm_costs, dtype=np.float64) * std
+        out, fixwin, best_fixed, assign_o, _, wsum = ops.rule_value(
+            prev[:, 0].contiguous(), stat, theta, table, coef, self.library, self.dt, quantiles, wt, cost=cost,
+            arm_cost=ac, maximize=maximize, assign=assign_t, group=group, n_groups=n_groups, weighting=weighting,
+            seed=use_seed, method=self.integrator, drop_below=0.0, T=wt.size(-1))
+        return effect.from_rule_value(out, fixwin, best_fixed, assign_o, wsum, quantiles, shift=mean * wtot,
+                                      scale=std)
 
     # ------------------------------------------------------------------ rollout (A8)
     def _predict_device(self, dataset, tau=1):
