@@ -2194,7 +2194,8 @@ struct RefitArgs {
 // Accumulation order (j ascending per arm) is that of the reference's term sum.
 template <int NARM>
 __device__ __forceinline__ void affine_rates_regs(const LibDesc& lib, const double (&cv)[NARM][INSITE_MAX_TERMS], int A,
-                                                  double drop, const double* uu, double* alpha, double* beta);
+                                                  double drop, const double* uu, double* alpha, double* beta,
+                                                  const int* ucv = nullptr);
 template <int NARM>
 __device__ __forceinline__ void load_coef_rows(const LibDesc& lib, const double* cbase, int A,
                                                double (&cv)[NARM][INSITE_MAX_TERMS]) {
@@ -2215,13 +2216,22 @@ __device__ __forceinline__ void affine_rates(const LibDesc& lib, const double* c
 }
 template <int NARM>
 __device__ __forceinline__ void affine_rates_regs(const LibDesc& lib, const double (&cv)[NARM][INSITE_MAX_TERMS], int A,
-                                                  double drop, const double* uu, double* alpha, double* beta) {
+                                                  double drop, const double* uu, double* alpha, double* beta,
+                                                  const int* ucv) {
 #pragma unroll
   for (int a = 0; a < NARM; ++a) alpha[a] = beta[a] = 0.0;
 #pragma unroll
   for (int j = 0; j < INSITE_MAX_TERMS; ++j) {
     if (j < lib.F) {
-      const int code = lib.ucode[j];
+      // The column code is decoded where it is used.  Every test on it (three exponent loops' entry guards and trip
+      // counts, the x exponent) is uniform and launch-invariant, so a caller that runs this once per rollout range
+      // had all 7 x 9 of them hoisted to the wave's start as SGPR pairs, spilled to VGPR lanes there (~220
+      // v_writelane) and read back in every range (~250 v_readlane); behind the opaque copy they are one s_bfe and
+      // one s_cmp each, next to the branch that needs them.
+      // ucv: the codes kept in VGPRs by a caller with many ranges (one v_readfirstlane a column; the kernel argument's
+      // eight dwords were reloaded from their spill lanes, all eight, for every column)
+      int code = ucv ? __builtin_amdgcn_readfirstlane(ucv[j]) : lib.ucode[j];
+      asm volatile("" : "+s"(code));
       const double m = monomial_code(code & 0xffffff, uu);
       const bool lin = (code >> 24) != 0;
 #pragma unroll
@@ -2462,6 +2472,9 @@ constexpr int kRollAG = 4;  // arm groups in flight (the rollout's arm ring)
 #ifndef INSITE_ROLL_SMASK
 #define INSITE_ROLL_SMASK 1  // 2-arm bit rollouts: the step's arm bits as the lane mask (rollout_bits_range)
 #endif
+#ifndef INSITE_ROLL_MRING
+#define INSITE_ROLL_MRING 1  // the step masks in one ring refilled in halves (0: two sets and a copy per chunk)
+#endif
 // A rollout range's per-lane inputs, requested ahead (rollout_units: the NEXT range's before this range's stores):
 // vmcnt counts stores too and completes in order, so inputs loaded at a range's start made the wave wait for every
 // store of the previous range still in flight -- one drained store queue per tile change.
@@ -2489,7 +2502,8 @@ template <int METHOD, int NARM, int PR, bool SR = false, bool PF = false>
 __device__ __forceinline__ void rollout_bits_range(const RolloutArgs& ra, const LibDesc& lib, const int lane,
                                                    const int64_t tile, const int g_begin, const int g_end,
                                                    const RefitArgs rf = RefitArgs{}, const RollPre* pre = nullptr,
-                                                   const double (*cvp)[NARM][INSITE_MAX_TERMS] = nullptr) {
+                                                   const double (*cvp)[NARM][INSITE_MAX_TERMS] = nullptr,
+                                                   const int* ucp = nullptr) {
   static_assert(!PF || (PR == 0 && !SR), "prefetched inputs: the global-coefficient range form");
   // rf by value: the address of the kernel's by-value argument would put a copy of it in scratch
   constexpr bool PERROW = PR == 1;
@@ -2541,7 +2555,17 @@ __device__ __forceinline__ void rollout_bits_range(const RolloutArgs& ra, const 
       if (act && rf.iters_out) rf.iters_out[p] = fit ? it : -2;
       affine_rates_regs<NARM>(lib, cv, ra.A, ra.drop, uu, al, be);
     } else if constexpr (PF) {
-      affine_rates_regs<NARM>(lib, *cvp, ra.A, ra.drop, uu, al, be);
+      // the wave's rows, opaque per range: the drop tests on them are launch-invariant too, and hoisted out of the
+      // range loop they came back as 14 spilled SGPR pairs; here each is one v_cmp beside its select
+      double cl[NARM][INSITE_MAX_TERMS];
+#pragma unroll
+      for (int a = 0; a < NARM; ++a)
+#pragma unroll
+        for (int j = 0; j < INSITE_MAX_TERMS; ++j) {
+          cl[a][j] = (*cvp)[a][j];
+          asm volatile("" : "+v"(cl[a][j]));
+        }
+      affine_rates_regs<NARM>(lib, cl, ra.A, ra.drop, uu, al, be, ucp);
     } else {
       affine_rates<NARM>(lib, ra.coef + (PERROW ? pc * ra.coef_stride : 0), ra.A, ra.drop, uu, al, be);
     }
@@ -2633,38 +2657,82 @@ __device__ __forceinline__ void rollout_bits_range(const RolloutArgs& ra, const 
         const double y0 = fma(A0, y, B0), y1 = fma(A1, y, B1);
         y = b ? y1 : y0;
       };
-      // the next chunk's masks are requested after the chunk's first step has used its own: scalar loads return out of
-      // order, so a use of mc[] with loads outstanding waits for all of them (lgkmcnt(0)); issued behind that first use
-      // (sched_barrier) they stay in flight for the rest of the chunk.  (Two mask sets used in turn instead of the
-      // copy raised the kernel's SGPR spills into this loop.)
-      uint64_t mc[kTG], mn[kTG];
+      // The masks live in ONE ring of kTG SGPR pairs (slot i = step k0 + i of the chunk), refilled in halves behind the
+      // steps that free them: slots [kTG/2, kTG) of this chunk once its step 0 has used its mask, slots [0, kTG/2) of
+      // the next chunk once step kTG/2 has.  Scalar loads return out of order, so a use of a slot with loads
+      // outstanding waits for all of them (lgkmcnt(0)): each refill is issued right behind the first use of the other
+      // half (sched_barrier) and stays in flight for that half's remaining steps.  INSITE_ROLL_MRING=0 (A/B): two mask
+      // sets, the whole next chunk requested behind step 0 and copied over at the chunk's end -- twice the live pairs
+      // (the kernel's SGPR spills around this loop) and kTG s_mov_b64 a chunk for twice the distance.
+      constexpr int kH = kTG / 2;
+      static_assert(kTG % 2 == 0, "the mask ring is refilled in halves");
+      // dst[j] = the mask of step min(kf + j, klast), j < kH: one 64-bit row address per half, the rows behind it at
+      // 32-bit offsets (the s_load's offset register; kTG rows stay below 2^31 bytes, the entry points' kTmMaxLd check)
+      // -- per mask a min, a multiply and the load, where mload's clamped 64-bit product per mask was 11 scalar
+      // instructions a step, more than the step's own five
+      const unsigned arow32 = (unsigned)arow;
+      auto mload_half = [&](uint64_t* dst, int kf) {
+        const int kb = kf < klast ? kf : klast;
+        const char* hb = ab + (int64_t)kb * arow;
+        const unsigned rem = (unsigned)(klast - kb);
 #pragma unroll
-      for (int i = 0; i < kTG; ++i) mc[i] = mload(i);
-      for (int k0 = 0; k0 < kend; k0 += kTG) {
-        auto next_masks = [&]() {
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int i = 0; i < kTG; ++i) mn[i] = mload(k0 + kTG + i);
-          __builtin_amdgcn_sched_barrier(0);
-        };
-        if (k0 >= kbeg) {  // uniform: stored steps (kbeg is a multiple of kRollGS)
-          const __amdgpu_buffer_rsrc_t ys = y_rsrc(k0);
-#pragma unroll
-          for (int i = 0; i < kTG; ++i) {
-            step2(mc[i]);
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, y), ys, yoff + (unsigned)(i * ra.ldy * 8), 0,
-                                                  kStoreAux);
-            if (i == 0) next_masks();
-          }
-        } else {  // before the range: integrate only
-#pragma unroll
-          for (int i = 0; i < kTG; ++i) {
-            if (INSITE_ABL_ROLL != 2) step2(mc[i]);
-            if (i == 0) next_masks();
+        for (int j = 0; j < kH; ++j) {
+          if (INSITE_ABL_ROLL == 3) {
+            dst[j] = mload(kf + j);
+          } else {
+            const cu32p q = (cu32p)(hb + ((unsigned)j < rem ? (unsigned)j : rem) * arow32);
+            dst[j] = (uint64_t)q[0] | ((uint64_t)q[1] << 32);
           }
         }
+      };
+      int k0 = 0;
+#if INSITE_ROLL_MRING
+      uint64_t mc[kTG];
+      mload_half(mc, 0);
+      auto refill = [&](int i) {  // behind step i's use of its own mask
+        if (i != 0 && i != kH) return;
+        __builtin_amdgcn_sched_barrier(0);
+        if (i == 0) mload_half(mc + kH, k0 + kH);
+        else mload_half(mc, k0 + kTG);
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      auto chunk_end = [&]() {};
+#else
+      uint64_t mc[kTG], mn[kTG];
+      mload_half(mc, 0);
+      mload_half(mc + kH, kH);
+      auto refill = [&](int i) {
+        if (i != 0) return;
+        __builtin_amdgcn_sched_barrier(0);
+        mload_half(mn, k0 + kTG);
+        mload_half(mn + kH, k0 + kTG + kH);
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      auto chunk_end = [&]() {
 #pragma unroll
         for (int i = 0; i < kTG; ++i) mc[i] = mn[i];
+      };
+#endif
+      // two loops, not one with a branch per chunk (kbeg is a multiple of kRollGS, so of kTG): merged, the two bodies'
+      // slots met in phi copies at the chunk's end, kTG s_mov_b64 again
+      for (; k0 < kbeg && k0 < kend; k0 += kTG) {  // before the range: integrate only
+#pragma unroll
+        for (int i = 0; i < kTG; ++i) {
+          if (INSITE_ABL_ROLL != 2) step2(mc[i]);
+          refill(i);
+        }
+        chunk_end();
+      }
+      for (; k0 < kend; k0 += kTG) {  // stored steps
+        const __amdgpu_buffer_rsrc_t ys = y_rsrc(k0);
+#pragma unroll
+        for (int i = 0; i < kTG; ++i) {
+          step2(mc[i]);
+          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, y), ys, yoff + (unsigned)(i * ra.ldy * 8), 0,
+                                                kStoreAux);
+          refill(i);
+        }
+        chunk_end();
       }
       return;
     }
@@ -2959,6 +3027,20 @@ __device__ __forceinline__ void rollout_units(const RolloutArgs& ra, const LibDe
   if (q >= q1) return;
   double cv[2][INSITE_MAX_TERMS];
   load_coef_rows<2>(lib, ra.coef, ra.A, cv);
+  // The rows are wave-uniform and live across every range of the wave: as 28 SGPRs (plus the 14 drop tests on them,
+  // an SGPR pair each) they were spilled to VGPR lanes at the wave's start and read back, two v_readlane a use, in
+  // every range's prologue.  The rollout role has the VGPRs to spare (the kernel's count is the gram role's), so they
+  // are pinned there; the products and the drop tests are the same operations on the same values, per lane.
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int j = 0; j < INSITE_MAX_TERMS; ++j) asm volatile("" : "+v"(cv[a][j]));
+  int uc[INSITE_MAX_TERMS];  // the library's column codes, likewise (affine_rates_regs)
+#pragma unroll
+  for (int j = 0; j < INSITE_MAX_TERMS; ++j) {
+    uc[j] = lib.ucode[j];
+    asm volatile("" : "+v"(uc[j]));
+  }
   int64_t tile = q / ng;
   int gb = (int)(q - tile * ng);
   int ge = q1 - q < (int64_t)(ng - gb) ? gb + (int)(q1 - q) : ng;
@@ -2972,7 +3054,7 @@ __device__ __forceinline__ void rollout_units(const RolloutArgs& ra, const LibDe
     const int gen = q1 - qn < (int64_t)(ng - gbn) ? gbn + (int)(q1 - qn) : ng;
     RollPre nxt;
     if (more) roll_pre_issue(ra, lib, lane, tn, gen, nxt);  // before this range's stores
-    rollout_bits_range<METHOD, 2, 0, false, true>(ra, lib, lane, tile, gb, ge, RefitArgs{}, &cur, &cv);
+    rollout_bits_range<METHOD, 2, 0, false, true>(ra, lib, lane, tile, gb, ge, RefitArgs{}, &cur, &cv, uc);
     if (!more) break;
     cur = nxt;
     q = qn;
