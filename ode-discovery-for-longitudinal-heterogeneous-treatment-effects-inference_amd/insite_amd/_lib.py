@@ -46,6 +46,7 @@ FEEDBACK_MINIMIZE, FEEDBACK_MAXIMIZE = 1, -1
 # include/insite_rulevalue.h
 RULEVALUE_ABI_VERSION = 1
 RULEVALUE_MAX_REPLICATES, RULEVALUE_MAX_RULES, RULEVALUE_MAX_GROUPS, RULEVALUE_MAX_QUANTILES = 4096, 16, 64, 16
+SEGBOOT_ABI_VERSION = 1   # include/insite_segboot.h
 METHOD_EULER, METHOD_RK4 = 0, 1
 LAYOUT_PATIENT_MAJOR, LAYOUT_TIME_MAJOR, LAYOUT_TIME_MAJOR_BITS, LAYOUT_PATIENT_MAJOR_BITS = 0, 1, 2, 3
 MAX_TERMS, MAX_STATICS, MAX_ARMS, MAX_STATE_DEGREE = 9, 3, 4, 1
@@ -176,6 +177,16 @@ RULEVALUE_SYMBOLS = (
     "insite_rulevalue_sums_f64",
     "insite_rulevalue_finalize_f64",
     "insite_rulevalue_f64",
+)
+
+# the extension header include/insite_segboot.h (same shared library, its own ABI version).  Not named *_EXPORTS
+# either; the Gram and the fit take a workspace before their outputs, the moments pass takes none
+SEGBOOT_SYMBOLS = (
+    "insite_segboot_abi_version",
+    "insite_segboot_moments_f64",
+    "insite_segboot_workspace_bytes",
+    "insite_segboot_gram_f64",
+    "insite_segboot_fit_f64",
 )
 
 
@@ -364,6 +375,16 @@ _SIGNATURES = {
                                            _c_i32, _c_i64, _c_i32, _c_i32, _c_i32, _c_f64, _c_i32, _c_i32, _c_f64,
                                            _c_i32, _vp, _c_i32, _c_i32, ctypes.c_uint32, _c_i64, _vp, _vp, _vp, _c_size,
                                            _vp, _vp, _vp, _c_i32, _vp, _c_i64, _vp, _vp, _vp]),
+    # insite_segboot.h
+    "insite_segboot_abi_version": (_c_i32, []),
+    "insite_segboot_moments_f64": (_c_i32, [_vp, _c_i64, _vp, _c_i64, _c_i32, _c_i32, _vp, _c_i64, _c_i32, _c_i32,
+                                            _c_f64, _vp, _vp]),
+    "insite_segboot_workspace_bytes": (_c_size, [_c_i64, _c_i32, _c_i32, _c_i32]),
+    "insite_segboot_gram_f64": (_c_i32, [_vp, _vp, _c_i64, _c_i64, _c_i32, _c_i32, _vp, _c_i32, _c_i32,
+                                         ctypes.c_uint32, _vp, _c_size, _vp, _vp, _vp]),
+    "insite_segboot_fit_f64": (_c_i32, [_vp, _vp, _c_i64, _c_i64, _c_i32, _c_i32, _vp, _c_i32, _c_i32,
+                                        ctypes.c_uint32, _c_f64, _c_f64, _c_i32, _c_i32, _vp, _c_size, _vp, _vp, _vp,
+                                        _vp, _vp, _vp]),
 }
 
 # (getter, the version these bindings were written for, the label of the mismatch message)
@@ -378,6 +399,7 @@ _ABI_VERSIONS = (
     ("insite_policy_abi_version", POLICY_ABI_VERSION, "policy "),
     ("insite_feedback_abi_version", FEEDBACK_ABI_VERSION, "feedback "),
     ("insite_rulevalue_abi_version", RULEVALUE_ABI_VERSION, "rulevalue "),
+    ("insite_segboot_abi_version", SEGBOOT_ABI_VERSION, "segboot "),
 )
 
 

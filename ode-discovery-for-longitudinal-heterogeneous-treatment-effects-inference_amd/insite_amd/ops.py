@@ -884,6 +884,141 @@ def plan_sindy_bootstrap(mom, u, arm, rows, lib, n_replicates, threshold, optimi
     return Plan(name, args, dev, out, keep)
 
 
+def _prep_segment_moments(x, arm, seq_len, dt, n_arms, fd, out, layout):
+    """Validate the inputs of the segment moments pass and pack the C arguments (insite_segboot.h)."""
+    if layout not in LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(LAYOUTS)}")
+    if fd not in SEGMENT_FD_KINDS:
+        raise ValueError(f"fd must be one of {sorted(SEGMENT_FD_KINDS)}")
+    _dev("x", x, torch.float64, 2)
+    _dev("arm", arm, torch.int8, 2)
+    _dev("seq_len", seq_len, torch.int32, 1)
+    if not 1 <= n_arms <= _lib.MAX_ARMS:
+        raise ValueError(f"n_arms must be in [1, {_lib.MAX_ARMS}]")
+    N = seq_len.numel()
+    if layout == "time":
+        n_steps = x.size(0)
+        if x.size(1) < N or arm.size(1) < N or arm.size(0) < n_steps - 1:
+            raise ValueError("time-major x must be [n_steps, >=N] and arm [>=n_steps-1, >=N]")
+    else:
+        n_steps = x.size(1)
+        if x.size(0) != N or arm.size(0) != N or arm.size(1) < n_steps - 1:
+            raise ValueError("patient-major x must be [N, n_steps] and arm [N, >=n_steps-1]")
+    if n_steps < 1:
+        raise ValueError("need at least one stored sample")
+    dev = x.device
+    if out is None:
+        out = torch.zeros((N, n_arms, 5), dtype=torch.float64, device=dev)
+    _dev("out", out, torch.float64)
+    if tuple(out.shape) != (N, n_arms, 5) or not out.is_contiguous():
+        raise ValueError("out must be a contiguous [N, n_arms, 5] tensor")
+    args = (_p(x), max(x.stride(0), 1), _p(arm), max(arm.stride(0), 1), LAYOUTS[layout], n_steps, _p(seq_len), N,
+            n_arms, SEGMENT_FD_KINDS[fd], float(dt), _p(out))
+    return "insite_segboot_moments_f64", args, dev, out, (x, arm, seq_len, out)
+
+
+def segment_moments(x: torch.Tensor, arm: torch.Tensor, seq_len: torch.Tensor, dt: float, n_arms: int = 4,
+                    fd: str = "order1", out: torch.Tensor | None = None, layout: str = "patient"):
+    """Per-(patient, arm) moments of the treatment-segment cut (insite_segboot_moments_f64): arrays as
+    ``gram_segments``.  Returns mom [N, n_arms, 5] = {count, sum x, sum x^2, sum x_dot, sum x_dot x} over the rows
+    that the patient's segments add to the arm; an arm the patient never visits is five zeros."""
+    return _run(_prep_segment_moments(x, arm, seq_len, dt, n_arms, fd, out, layout))
+
+
+def plan_segment_moments(x, arm, seq_len, dt, n_arms=4, fd="order1", out=None, layout="patient") -> Plan:
+    """``segment_moments`` as a prepared launch; ``plan.out`` = mom."""
+    return Plan(*_prep_segment_moments(x, arm, seq_len, dt, n_arms, fd, out, layout))
+
+
+def _prep_segboot(mom, u, lib, n_replicates, seed, patient_offset, workspace, out, fit_args=None):
+    """Validate the inputs of the segment bootstrap and pack the C arguments (insite_segboot.h: the workspace stands
+    before the outputs)."""
+    L = _lib.load()
+    _dev("mom", mom, torch.float64, 3)
+    N, n_arms = mom.size(0), mom.size(1)
+    if mom.size(2) != 5 or not mom.is_contiguous():
+        raise ValueError("mom must be a contiguous [N, n_arms, 5] tensor")
+    if not 1 <= n_arms <= _lib.MAX_ARMS:
+        raise ValueError(f"n_arms must be in [1, {_lib.MAX_ARMS}]")
+    if lib.n_statics:
+        _dev("u", u, torch.float64, 2)
+        if u.size(0) != N or u.size(1) != lib.n_statics or u.stride(0) != lib.n_statics:
+            raise ValueError("u must be a contiguous [N, n_statics] tensor")
+    R = int(n_replicates)
+    if not 1 <= R <= _lib.BOOT_MAX_REPLICATES:
+        raise ValueError(f"n_replicates must be in [1, {_lib.BOOT_MAX_REPLICATES}]")
+    if not 0 <= int(seed) < 2 ** 32:
+        raise ValueError("seed must be a uint32")
+    if int(patient_offset) < 0:
+        raise ValueError("patient_offset must be >= 0")
+    F = lib.n_terms
+    dev = mom.device
+    ws = _ws(workspace, dev, "disc").get(L.insite_segboot_workspace_bytes(N, n_arms, F, R), dev)
+    tab = lib.ctypes_table()
+    head = (_p(mom), _p(u) if lib.n_statics else ctypes.c_void_p(0), int(patient_offset), N, lib.n_statics, n_arms,
+            tab.ctypes.data_as(ctypes.c_void_p), F, R, int(seed))
+    n_out = 2 if fit_args is None else 5
+    if out is None:
+        out = (torch.zeros((R, n_arms, F, F), dtype=torch.float64, device=dev),
+               torch.zeros((R, n_arms, F), dtype=torch.float64, device=dev))
+        if fit_args is not None:
+            out = (torch.zeros((R, n_arms, F), dtype=torch.float64, device=dev),
+                   torch.zeros((R, n_arms, F), dtype=torch.int8, device=dev),
+                   torch.zeros((R, n_arms), dtype=torch.int32, device=dev)) + out
+    if len(out) != n_out:
+        raise ValueError(f"out must hold {n_out} tensors")
+    for t, shape in zip(out[-2:], ((R, n_arms, F, F), (R, n_arms, F))):
+        _dev("out", t, torch.float64)
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError("G / b outputs must be contiguous [R, n_arms, F, F] / [R, n_arms, F]")
+    keep = (mom, u, tab, ws, *out)
+    if fit_args is None:
+        G, b = out
+        return "insite_segboot_gram_f64", head + (_p(ws), ws.numel(), _p(G), _p(b)), dev, out, keep
+    threshold, alpha, max_iter, unbias = fit_args
+    coef, mask, iters, G, b = out
+    if (tuple(coef.shape) != (R, n_arms, F) or tuple(mask.shape) != (R, n_arms, F) or iters.numel() != R * n_arms
+            or not (coef.is_contiguous() and mask.is_contiguous() and iters.is_contiguous())):
+        raise ValueError("coef / mask / iters outputs must be contiguous [R, n_arms, F] / [R, n_arms, F] / [R, n_arms]")
+    _dev("coef", coef, torch.float64)
+    _dev("mask", mask, torch.int8)
+    _dev("iters", iters, torch.int32)
+    args = head + (float(threshold), float(alpha), int(max_iter), int(bool(unbias)), _p(ws), ws.numel(), _p(G), _p(b),
+                   _p(coef), _p(mask), _p(iters))
+    return "insite_segboot_fit_f64", args, dev, out, keep
+
+
+def segboot_gram(mom: torch.Tensor, u: torch.Tensor, lib: PolyLibrary, n_replicates: int, seed: int = 0,
+                 patient_offset: int = 0, workspace: Workspace | None = None, out: tuple | None = None):
+    """The Gram systems of ``n_replicates`` patient-level Poisson bootstrap replicates of the treatment-segment
+    regression from ``segment_moments``' mom [N, n_arms, 5] (insite_segboot_gram_f64).  A patient contributes to every
+    arm it has rows in (count > 0) under ONE weight per replicate, the weight ``bootstrap_gram`` draws for
+    (seed, replicate, patient_offset + p); replicate 0 has weight 1 everywhere.  Returns (G[R,A,F,F], b[R,A,F])."""
+    return _run(_prep_segboot(mom, u, lib, n_replicates, seed, patient_offset, workspace, out))
+
+
+def sindy_bootstrap_segments(mom: torch.Tensor, u: torch.Tensor, lib: PolyLibrary, n_replicates: int,
+                             threshold: float, alpha: float = 0.5, max_iter: int = 100, unbias: bool = True,
+                             seed: int = 0, patient_offset: int = 0, workspace: Workspace | None = None,
+                             out: tuple | None = None):
+    """``segboot_gram`` followed on the stream by STLSQ on the R n_arms systems (insite_segboot_fit_f64).  Returns
+    (coef[R,A,F], mask[R,A,F], iters[R,A], G[R,A,F,F], b[R,A,F])."""
+    return _run(_prep_segboot(mom, u, lib, n_replicates, seed, patient_offset, workspace, out,
+                              (threshold, alpha, max_iter, unbias)))
+
+
+def plan_segboot_gram(mom, u, lib, n_replicates, seed=0, patient_offset=0, workspace=None, out=None) -> Plan:
+    """``segboot_gram`` as a prepared launch; ``plan.out`` = (G, b)."""
+    return Plan(*_prep_segboot(mom, u, lib, n_replicates, seed, patient_offset, _plan_ws(workspace), out))
+
+
+def plan_sindy_bootstrap_segments(mom, u, lib, n_replicates, threshold, alpha=0.5, max_iter=100, unbias=True, seed=0,
+                                  patient_offset=0, workspace=None, out=None) -> Plan:
+    """``sindy_bootstrap_segments`` as a prepared launch; ``plan.out`` = (coef, mask, iters, G, b)."""
+    return Plan(*_prep_segboot(mom, u, lib, n_replicates, seed, patient_offset, _plan_ws(workspace), out,
+                               (threshold, alpha, max_iter, unbias)))
+
+
 def _quantiles(quantiles, cap):
     q = np.ascontiguousarray([float(v) for v in quantiles], dtype=np.float64)
     if not 1 <= q.size <= cap:

@@ -35,7 +35,9 @@ itself still raises ``NotImplementedError``.  ``bootstrap`` / ``bootstrap_irregu
 patient-level Poisson resamples from the per-patient moments (``insite_sindy_bootstrap_f64``) and
 ``predict_interval`` turns the replicates into pointwise prediction bands.  ``predict_bands`` and
 ``treatment_effect`` give the bands of every row, and of the paired effect of two treatment plans, without
-materialising the replicate trajectories (``insite_effect_bands_f64``).
+materialising the replicate trajectories (``insite_effect_bands_f64``).  On the treatment-segment
+datasets ``bootstrap_segments`` draws the ensemble (one weight per patient for all of their segments,
+``insite_segboot_fit_f64``) and opens the same methods.
 """
 from __future__ import annotations
 
@@ -420,10 +422,16 @@ class SINDY:
     # ------------------------------------------------------------------ patient-level bootstrap
     IRREGULAR_WINDOW = {"nonuniform2": 3, "nonuniform4": 5}   # samples the Lagrange derivative needs
 
-    def _check_bootstrap(self, what):
-        if self.joint_model or self.segment_mode or self.library.state_degree > 1:
-            raise NotImplementedError(f"{what} covers the per-arm EQ_4 model over the affine library (not the "
-                                      "joint, treatment-segment or degree-4 modes)")
+    def _check_bootstrap(self, what, resample=False):
+        """``resample``: ``what`` draws an ensemble of the one-arm-per-patient model itself (``bootstrap``,
+        ``bootstrap_irregular``).  Every other caller consumes ``bootstrap_``; a treatment-segment model may, once
+        ``bootstrap_segments`` has stored its own ensemble (``bootstrap_mode_ == "segments"``)."""
+        if self.joint_model or self.library.state_degree > 1:
+            raise NotImplementedError(f"{what} covers the per-arm model over the affine library (not the joint or "
+                                      "degree-4 modes)")
+        if self.segment_mode and (resample or getattr(self, "bootstrap_mode_", None) != "segments"):
+            raise NotImplementedError(f"{what}: a treatment-segment model (cancer_sim, EQ_5_*) takes its ensemble "
+                                      "from bootstrap_segments()")
 
     def _bootstrap_moments(self, mom, u, arm, rows, min_rows, n_replicates, seed, quantiles, optimizer, max_iter):
         """The replicates' fits from per-patient moments with the model's own solver parameters -> bootstrap_."""
@@ -433,6 +441,37 @@ class SINDY:
                                                       seed=seed, n_arms=self.dim_treatments, min_rows=min_rows)
         self.bootstrap_ = bootstrap.summarize(coef, mask, quantiles, seed=int(seed))
         self.bootstrap_iters_ = iters
+        self.bootstrap_mode_ = "arms"
+        return self.bootstrap_
+
+    def bootstrap_segments(self, train_f, n_replicates=256, seed=0, quantiles=(0.025, 0.5, 0.975)):
+        """``bootstrap`` for the treatment-segment datasets (cancer_sim, EQ_5_*; insite_segboot.h):
+        ``n_replicates`` refits of the per-arm segment regression of ``fit``, each on the cohort with every patient
+        -- all of its segments, in every arm -- weighted by one Poisson(1) count; replicate 0 has weight 1 everywhere
+        (the fit itself).  Stores and returns ``self.bootstrap_`` and marks it as the segment model's own, which
+        opens ``predict_interval``, ``predict_bands``, ``treatment_effect``, ``average_effect``,
+        ``predict_average``, ``choose_plan``, ``policy_value``, ``evaluate_rules`` and ``rule_value`` to this model;
+        the fitted model is not touched."""
+        if not self.segment_mode:
+            raise NotImplementedError("bootstrap_segments covers the treatment-segment datasets (cancer_sim, "
+                                      "EQ_5_*); the EQ_4 family has bootstrap()")
+        if self.weak_form or self.joint_model or self.library.state_degree > 1:
+            raise NotImplementedError("bootstrap_segments covers the per-arm strong-form segment model over the "
+                                      "affine library (not the weak_form, joint_model or degree-4 modes)")
+        self.prepare_data()
+        x, u, arm, sl = self.de_format_segments(train_f)
+        fd = "smoothed1" if self.use_smoothed_finite_difference else "order1"
+        mom = ops.segment_moments(x, arm, sl, self.dt, n_arms=self.dim_treatments, fd=fd)
+        coef, mask, iters, _, _ = ops.sindy_bootstrap_segments(mom, u, self.library, n_replicates,
+                                                               self.sindy_threshold, alpha=self.sindy_alpha,
+                                                               max_iter=100, unbias=True, seed=seed)
+        empty = np.nonzero(mom[:, :, 0].sum(0).cpu().numpy() == 0)[0]   # replicate 0's sample count per arm
+        if empty.size:
+            raise ValueError(f"treatment arm(s) {empty.tolist()} have no training segments "
+                             "(pysindy cannot fit an empty trajectory list)")
+        self.bootstrap_ = bootstrap.summarize(coef, mask, quantiles, seed=int(seed))
+        self.bootstrap_iters_ = iters
+        self.bootstrap_mode_ = "segments"
         return self.bootstrap_
 
     def bootstrap(self, train_f, n_replicates=256, seed=0, quantiles=(0.025, 0.5, 0.975)):
@@ -443,7 +482,7 @@ class SINDY:
         returns ``self.bootstrap_`` (``bootstrap.BootstrapResult``); the fitted model is not touched.  Under
         ``weak_form`` the subdomain centres are drawn as ``fit`` draws them: they are the fitted model's only with a
         fixed ``weak_seed``."""
-        self._check_bootstrap("bootstrap")
+        self._check_bootstrap("bootstrap", resample=True)
         self.prepare_data()
         x, u, arm, rows = self.de_format(train_f)
         if self.weak_form:
@@ -465,7 +504,7 @@ class SINDY:
     def bootstrap_irregular(self, x, t_obs, n_obs, u, arm, fd="nonuniform4", validate=True, n_replicates=256, seed=0,
                             quantiles=(0.025, 0.5, 0.975)):
         """``bootstrap`` on the irregular pass's per-patient moments (the arguments of ``fit_irregular``)."""
-        self._check_bootstrap("bootstrap_irregular")
+        self._check_bootstrap("bootstrap_irregular", resample=True)
         mom = ops.gram_irregular(x, t_obs, n_obs, u, arm, self.library, n_arms=self.dim_treatments, fd=fd,
                                  moments=True, validate=validate)[2]
         return self._bootstrap_moments(mom, u, arm, n_obs, self.IRREGULAR_WINDOW[fd], n_replicates, seed, quantiles,
