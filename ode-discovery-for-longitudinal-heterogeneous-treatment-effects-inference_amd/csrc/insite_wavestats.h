@@ -258,4 +258,39 @@ __device__ __forceinline__ void ef_series_stats(const double (&v)[NB][V], const 
   }
 }
 
+// The sort and the moments of one series whose valid values are all finite, about a reference y (score_sums_kernel,
+// insite_score.hip): key = the ascending sort of the n valid values (the padding +Inf behind them), mean = the shifted
+// mean of ef_series_stats, and in every lane the wave totals m2 = sum (v - mean)^2, abs_dev = sum |v - y| and
+// gini = sum_i (2 i - n + 1) (key_i - mean) over the sorted index i = lane V + slot < n.  Two wave reductions of two
+// sums each, in ef_series_stats' fixed order: the lane's slots ascending, then the butterfly.
+template <int V>
+__device__ __forceinline__ void ef_sorted_moments(const double (&v)[V], const bool (&valid)[V], int lane, int n,
+                                                  double y, double (&key)[1][V], double& mean, double& m2,
+                                                  double& abs_dev, double& gini) {
+  const double inf = std::numeric_limits<double>::infinity();
+  const double c = readlane_f64(v[0], 1);
+  double acc[2] = {0.0, 0.0};
+#pragma unroll
+  for (int s = 0; s < V; ++s) {
+    key[0][s] = valid[s] ? v[s] : inf;
+    acc[0] += valid[s] ? v[s] - c : 0.0;
+    acc[1] += valid[s] ? fabs(v[s] - y) : 0.0;
+  }
+  ef_wave_sum<2>(acc, lane);
+  mean = c + acc[0] / (double)n;
+  abs_dev = acc[1];
+  ef_sort<1, V>(key, lane);
+  acc[0] = acc[1] = 0.0;
+#pragma unroll
+  for (int s = 0; s < V; ++s) {
+    const double d = v[s] - mean;
+    acc[0] += valid[s] ? d * d : 0.0;
+    const int i = lane * V + s;
+    acc[1] += i < n ? (double)(2 * i - n + 1) * (key[0][s] - mean) : 0.0;
+  }
+  ef_wave_sum<2>(acc, lane);
+  m2 = acc[0];
+  gini = acc[1];
+}
+
 }  // namespace

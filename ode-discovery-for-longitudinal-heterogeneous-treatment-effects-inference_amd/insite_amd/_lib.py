@@ -47,6 +47,8 @@ FEEDBACK_MINIMIZE, FEEDBACK_MAXIMIZE = 1, -1
 RULEVALUE_ABI_VERSION = 1
 RULEVALUE_MAX_REPLICATES, RULEVALUE_MAX_RULES, RULEVALUE_MAX_GROUPS, RULEVALUE_MAX_QUANTILES = 4096, 16, 64, 16
 SEGBOOT_ABI_VERSION = 1   # include/insite_segboot.h
+# include/insite_score.h
+SCORE_ABI_VERSION, SCORE_MAX_REPLICATES, SCORE_MAX_LEVELS, SCORE_MAX_BINS, SCORE_MAX_GROUPS = 1, 512, 8, 32, 64
 METHOD_EULER, METHOD_RK4 = 0, 1
 LAYOUT_PATIENT_MAJOR, LAYOUT_TIME_MAJOR, LAYOUT_TIME_MAJOR_BITS, LAYOUT_PATIENT_MAJOR_BITS = 0, 1, 2, 3
 MAX_TERMS, MAX_STATICS, MAX_ARMS, MAX_STATE_DEGREE = 9, 3, 4, 1
@@ -187,6 +189,14 @@ SEGBOOT_SYMBOLS = (
     "insite_segboot_workspace_bytes",
     "insite_segboot_gram_f64",
     "insite_segboot_fit_f64",
+)
+
+# the extension header include/insite_score.h (same shared library, its own ABI version).  Not named *_EXPORTS
+# either; the sums call takes a workspace before its output (the header says why)
+SCORE_SYMBOLS = (
+    "insite_score_abi_version",
+    "insite_score_workspace_bytes",
+    "insite_score_sums_f64",
 )
 
 
@@ -385,6 +395,12 @@ _SIGNATURES = {
     "insite_segboot_fit_f64": (_c_i32, [_vp, _vp, _c_i64, _c_i64, _c_i32, _c_i32, _vp, _c_i32, _c_i32,
                                         ctypes.c_uint32, _c_f64, _c_f64, _c_i32, _c_i32, _vp, _c_size, _vp, _vp, _vp,
                                         _vp, _vp, _vp]),
+    # insite_score.h
+    "insite_score_abi_version": (_c_i32, []),
+    "insite_score_workspace_bytes": (_c_size, [_c_i64, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32]),
+    "insite_score_sums_f64": (_c_i32, [_vp, _vp, _vp, _c_i64, _vp, _vp, _c_i32, _c_i64, _c_i32, _c_i32, _c_i32, _c_f64,
+                                       _c_i32, _c_i32, _c_f64, _c_i32, _vp, _c_i64, _vp, _c_i64, _vp, _c_i32, _vp,
+                                       _c_i32, _c_i32, _vp, _c_size, _vp, _c_i64, _vp]),
 }
 
 # (getter, the version these bindings were written for, the label of the mismatch message)
@@ -400,6 +416,7 @@ _ABI_VERSIONS = (
     ("insite_feedback_abi_version", FEEDBACK_ABI_VERSION, "feedback "),
     ("insite_rulevalue_abi_version", RULEVALUE_ABI_VERSION, "rulevalue "),
     ("insite_segboot_abi_version", SEGBOOT_ABI_VERSION, "segboot "),
+    ("insite_score_abi_version", SCORE_ABI_VERSION, "score "),
 )
 
 

@@ -317,3 +317,68 @@ def from_rule_value(out: torch.Tensor, fixwin: torch.Tensor, best_fixed: torch.T
     return RuleValueResult(point=res[:, 0], mean=res[:, 1], std=res[:, 2], quantiles=res[:, 3:], fixwin=fixwin,
                            best_fixed=best_fixed, assign=assign, weight_sum=wsum, q=tuple(float(v) for v in q),
                            series=rule_value_series(K), n_rules=K)
+
+
+@dataclasses.dataclass
+class EnsembleScore:
+    """The bootstrap ensemble scored against observed outcomes (``ops.ensemble_score``, include/insite_score.h,
+    DESIGN.md §9p), per group and step.  ``n``, ``n_bad`` [G, T]: the scored cells and the observed cells with a
+    non-finite replicate; ``rmse_point``, ``rmse_mean``: of the point model and of the ensemble mean; ``spread`` =
+    sqrt(mean ensemble variance) (calibrated against ``rmse_mean``: under-dispersed when smaller); ``crps``: the mean
+    CRPS of the ensemble's empirical distribution; ``coverage``, ``width``, ``interval_score`` [G, L, T]: of the
+    central bands of ``levels``; ``pit_hist`` [G, B, T]: the rank histogram as frequencies.  ``pooled``: the same
+    names without the step dimension, from the sums added over the steps first.  A cell count of 0 gives NaN.
+    ``sums``: the additive sums all of it was made from."""
+    n: torch.Tensor
+    n_bad: torch.Tensor
+    rmse_point: torch.Tensor
+    rmse_mean: torch.Tensor
+    spread: torch.Tensor
+    crps: torch.Tensor
+    coverage: torch.Tensor
+    width: torch.Tensor
+    interval_score: torch.Tensor
+    pit_hist: torch.Tensor
+    pooled: dict
+    sums: torch.Tensor
+    levels: tuple
+    n_bins: int
+    scale: float = 1.0
+
+    def merge(self, other: "EnsembleScore") -> "EnsembleScore":
+        """The score of the union of two shards: their sums added (equal levels, bins, scale and shape)."""
+        if (self.levels != other.levels or self.n_bins != other.n_bins or self.scale != other.scale
+                or self.sums.shape != other.sums.shape):
+            raise ValueError("merge needs scores of equal levels, bins, scale and shape")
+        return from_score(self.sums + other.sums.to(self.sums.device), self.levels, self.n_bins, self.scale)
+
+
+def _score_stats(s: torch.Tensor, L: int, B: int, scale: float) -> dict:
+    """s [G, S, ...] -> the statistics over the trailing dimensions (a cell count of 0: 0 / 0 = NaN)."""
+    n = s[:, 0]
+    lv = s[:, 6 + B:].reshape((s.size(0), L, 3) + tuple(s.shape[2:]))
+    nl = n[:, None]
+    return {
+        "n": n, "n_bad": s[:, 1],
+        "rmse_point": torch.sqrt(s[:, 2] / n) / scale,
+        "rmse_mean": torch.sqrt(s[:, 3] / n) / scale,
+        "spread": torch.sqrt(s[:, 4] / n) / scale,
+        "crps": s[:, 5] / n / scale,
+        "pit_hist": s[:, 6:6 + B] / nl,
+        "coverage": lv[:, :, 0] / nl,
+        "width": lv[:, :, 1] / nl / scale,
+        "interval_score": lv[:, :, 2] / nl / scale,
+    }
+
+
+def from_score(sums: torch.Tensor, levels, n_bins: int, scale: float = 1.0) -> EnsembleScore:
+    """``ops.ensemble_score``'s sums [G, 6 + B + 3 L, T] as an ``EnsembleScore`` in the scale x / scale: lengths
+    (RMSE, spread, CRPS, width, interval score) are divided by ``scale`` -- the squared sums by its square --, counts
+    and frequencies are left as they are.  The pooled figures add the sums over the steps first and divide after."""
+    levels = tuple(float(v) for v in levels)
+    L, B = len(levels), int(n_bins)
+    if sums.dim() != 3 or sums.size(1) != 6 + B + 3 * L:
+        raise ValueError("sums must be [G, 6 + n_bins + 3 n_levels, T]")
+    per = _score_stats(sums, L, B, float(scale))
+    pooled = _score_stats(sums.sum(dim=2), L, B, float(scale))
+    return EnsembleScore(pooled=pooled, sums=sums, levels=levels, n_bins=B, scale=float(scale), **per)

@@ -1127,6 +1127,89 @@ def plan_effect_bands(y0, u, arm_a, arm_b, coef, lib, dt, quantiles, method="eul
     return Plan(name, args, dev, out, keep)
 
 
+def score_rows(n_levels: int, n_bins: int) -> int:
+    """S of include/insite_score.h: the rows of the score sums."""
+    return 6 + int(n_bins) + 3 * int(n_levels)
+
+
+def _prep_ensemble_score(y0, u, arm, y_obs, active, coef, lib, dt, levels, n_bins, group, n_groups, method, substeps,
+                         drop_below, T, out, workspace):
+    """Validate the inputs of the ensemble score and pack the C arguments (insite_score.h)."""
+    L = _lib.load()
+    N, T, R, A = _check_ensemble(y0, u, arm, None, coef, lib, T, _lib.SCORE_MAX_REPLICATES)
+    F = lib.n_terms
+    _dev("y_obs", y_obs, torch.float64, 2)
+    if y_obs.size(0) != N or y_obs.size(1) < T:
+        raise ValueError("y_obs must be [N, >=T]")
+    if active is not None:
+        _dev("active", active, torch.int8, 2)
+        if active.size(0) != N or active.size(1) < T:
+            raise ValueError("active must be [N, >=T]")
+    lv = np.ascontiguousarray([float(v) for v in levels], dtype=np.float64)
+    if not 1 <= lv.size <= _lib.SCORE_MAX_LEVELS:
+        raise ValueError(f"between 1 and {_lib.SCORE_MAX_LEVELS} levels expected")
+    if not bool(np.all((lv > 0.0) & (lv < 1.0))):
+        raise ValueError("levels must lie strictly inside (0, 1)")
+    B = int(n_bins)
+    if not 1 <= B <= _lib.SCORE_MAX_BINS:
+        raise ValueError(f"n_bins must be in [1, {_lib.SCORE_MAX_BINS}]")
+    G = int(n_groups)
+    if not 1 <= G <= _lib.SCORE_MAX_GROUPS:
+        raise ValueError(f"n_groups must be in [1, {_lib.SCORE_MAX_GROUPS}]")
+    if group is not None:
+        _dev("group", group, torch.int32, 1)
+        if group.numel() != N:
+            raise ValueError("group must have one entry per row")
+    m, sub = _method(method, substeps)
+    dev = y0.device
+    S = score_rows(lv.size, B)
+    if out is None:
+        out = torch.zeros((G, S, T), dtype=torch.float64, device=dev)
+        ld_out = T
+    else:
+        _dev("out", out, torch.float64, 3)
+        ld_out = out.stride(1) if S > 1 else max(T, out.size(2))
+        if (tuple(out.shape[:2]) != (G, S) or out.size(2) < T or ld_out < out.size(2)
+                or (G > 1 and out.stride(0) != S * ld_out)):
+            raise ValueError(f"out must be {(G, S, T)} with a dense leading dimension (rows may be padded)")
+    ws_bytes = L.insite_score_workspace_bytes(N, T, A, F, R, G)
+    ws = _ws(workspace, dev, "scratch").get(ws_bytes, dev) if ws_bytes else None
+    tab = lib.ctypes_table()
+    args = (_p(y0), _p(u) if lib.n_statics else ctypes.c_void_p(0), _p(arm), arm.stride(0), _p(coef),
+            tab.ctypes.data_as(ctypes.c_void_p), F, N, T, lib.n_statics, A, float(dt), m, sub, float(drop_below), R,
+            _p(y_obs), y_obs.stride(0), _p(active), active.stride(0) if active is not None else 0, _p(group), G,
+            lv.ctypes.data_as(ctypes.c_void_p), lv.size, B, _p(ws), ws.numel() if ws is not None else 0, _p(out),
+            ld_out)
+    return "insite_score_sums_f64", args, dev, out, (y0, u, arm, y_obs, active, coef, group, tab, lv, ws, out)
+
+
+def ensemble_score(y0: torch.Tensor, u: torch.Tensor, arm: torch.Tensor, y_obs: torch.Tensor,
+                   active: torch.Tensor | None, coef: torch.Tensor, lib: PolyLibrary, dt: float, levels,
+                   n_bins: int = 10, group: torch.Tensor | None = None, n_groups: int = 1, method: str = "euler5",
+                   substeps: int | None = None, drop_below: float = 1e-3, T: int | None = None,
+                   out: torch.Tensor | None = None, workspace: Workspace | None = None):
+    """The bootstrap ensemble scored against observed outcomes (insite_score_sums_f64).
+
+    The inputs of ``effect_bands`` for one plan ``arm``, the observations y_obs f64 [N, >=T] (``y_obs[p, k]``: the
+    state after interval k, ``rollout``'s alignment), the mask active int8 [N, >=T] (None: every cell; a non-finite
+    observation is not scored either), the central band ``levels`` (each inside (0, 1)), ``n_bins`` of the rank
+    histogram and ``group`` int32 [N] (None: one group; ids outside [0, n_groups) exclude the row).  Returns the sums
+    [G, 6 + n_bins + 3 L, T] of include/insite_score.h, additive over the shards of a cohort;
+    ``effect.from_score`` turns them into coverage, width, interval score, PIT histogram, CRPS, spread and RMSE.  The
+    replicate trajectories never exist in memory.  With no rows nothing is written: a fresh output is zero."""
+    return _run(_prep_ensemble_score(y0, u, arm, y_obs, active, coef, lib, dt, levels, n_bins, group, n_groups, method,
+                                     substeps, drop_below, T, out, workspace))
+
+
+def plan_ensemble_score(y0, u, arm, y_obs, active, coef, lib, dt, levels, n_bins=10, group=None, n_groups=1,
+                        method="euler5", substeps=None, drop_below=1e-3, T=None, out=None, workspace=None) -> Plan:
+    """``ensemble_score`` as a prepared launch; ``plan.out`` = the sums."""
+    ws = workspace.claim("scratch") if workspace is not None else Workspace("scratch")
+    name, args, dev, out, keep = _prep_ensemble_score(y0, u, arm, y_obs, active, coef, lib, dt, levels, n_bins, group,
+                                                      n_groups, method, substeps, drop_below, T, out, ws)
+    return Plan(name, args, dev, out, keep)
+
+
 def _check_plans_weights(y0, plans, weights, cost, T, max_plans):
     """What the regimen choice and the policy value check first: y0 [N], the candidate plans int8 [K, T] (shared by
     the rows) or [K, N, >=T], the step weights f64 [T] or [N, >=T] and cost f64 [K] or None.  Returns

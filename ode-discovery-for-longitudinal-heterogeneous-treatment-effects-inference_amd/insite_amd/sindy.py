@@ -610,6 +610,36 @@ class SINDY:
                                method=self.integrator, drop_below=0.0, T=arm_a.size(1))
         return effect.from_bands(out, quantiles, shift=mean, scale=std)
 
+    # ------------------------------------------------------------------ scoring the bands
+    def score_bands(self, dataset, levels=(0.5, 0.9, 0.95), n_bins=10, groups=None, plan=None):
+        """How good the bands of ``bootstrap_`` are on a dataset with outcomes: per group (``groups`` as
+        ``average_effect``'s) and step, and pooled over the steps, the coverage, width and interval score of the
+        central bands of ``levels``, the rank (PIT) histogram with ``n_bins`` bins, the CRPS of the ensemble, its spread
+        and the RMSE of the point model and of the ensemble mean -- an ``effect.EnsembleScore``, lengths standardised
+        with the output's standard deviation.  Observations: ``unscaled_outputs`` (else ``outputs`` un-standardised)
+        over the cells of ``active_entries``; ``plan``: None (the dataset's own treatments) or a plan of
+        ``treatment_effect``.  One launch of ``ops.ensemble_score``: the [N, R, T] replicate rollouts never exist in
+        memory.  The ensemble carries the model's uncertainty only: on noisy outcomes under-coverage is the honest
+        answer."""
+        coef = self._effect_coef("score_bands")
+        d = dataset.data
+        N = d["current_treatments"].shape[0]
+        group, n_groups = self._groups(groups, N)
+        prev, stat, std, mean = self._unscaled_inputs(dataset)
+        arm = self._plan_arms(dataset, plan, "plan")
+        if "unscaled_outputs" in d:
+            y_obs = torch.as_tensor(np.ascontiguousarray(d["unscaled_outputs"][..., 0], dtype=np.float64),
+                                    device=self.device)
+        else:
+            y_obs = torch.as_tensor(np.ascontiguousarray(d["outputs"][..., 0], dtype=np.float64),
+                                    device=self.device) * std + mean
+        active = torch.as_tensor(np.ascontiguousarray(d["active_entries"][..., 0] != 0).astype(np.int8),
+                                 device=self.device)
+        sums = ops.ensemble_score(prev[:, 0].contiguous(), stat, arm, y_obs, active, coef, self.library, self.dt,
+                                  levels, n_bins=n_bins, group=group, n_groups=n_groups, method=self.integrator,
+                                  drop_below=0.0, T=arm.size(1))
+        return effect.from_score(sums, levels, n_bins, scale=std)
+
     # ------------------------------------------------------------------ regimen choice (DESIGN.md §9j)
     def _objective_weights(self, dataset, objective):
         """The step weights of ``choose_plan``: f64 [T] or [N, T] on the host."""
